@@ -11,8 +11,14 @@ MI355X: 15.1 GB reads + 34 GB table).  N > 1 -> BASELINE configs[3]'s per-GPU sh
 per GPU (rank r counts reads [r x 125 M, (r + 1) x 125 M): at N = 8 that IS the 1 B-read set), weak scaling.
 
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing else: set up, warm up, time --steps steps, write the outputs of the last
+step when --dump-outputs DIR is given (dump_outputs()), print the line.  --full adds everything else this file measures or
+checks, after the timed loop: verify, cpu_baseline, end_to_end, configs, cli below, and for N > 1 the merge's conservation
+check and single_gpu_same_share.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) -- SMALL: at most 6 KB, so that it fits whole into the
 8 KB tail the driver keeps of stdout (round 4's 23.5 KB line did not, and the driver recorded `parsed: null`).  The line
@@ -20,12 +26,12 @@ Prints ONE JSON line on rank 0 (contract in the task statement) -- SMALL: at mos
   roofline      algorithmic HBM bytes of the counting kernels / their HIP-event duration, vs 8 TB/s; the kernels
                 are NAMED from what ran (kh_stats.stage_ms), and tests/test_docs_drift.py holds the names to the
                 source and to the committed rocprofv3 kernel trace
-  verify        (N = 1, after the timed loop, outside it) exact counts of a 1/1024 key sample and the k-mer total
-                against the CPU oracle's scan of the same reads: the line says itself whether it is bit-exact
-  cpu_baseline  the krust-equivalent threaded CPU port (oracle/) timed on this host's cores on a bounded sample
+  verify        (--full or --verify; N = 1, after the timed loop, outside it) exact counts of a 1/1024 key sample and the
+                k-mer total against the CPU oracle's scan of the same reads: the line says itself whether it is bit-exact
+  cpu_baseline  (--full) the krust-equivalent threaded CPU port (oracle/) timed on this host's cores on a bounded sample
                 of the same reads, `optimised_value` beside it (rank 0, N=1 only).  A reported baseline only.
-  configs       BASELINE configs[1..4] (and a k = 19 twin of the headline): one flat row each
-  cli           the kmerust command line on S10M and S100M FASTQ files: wall seconds
+  configs       (--full) BASELINE configs[1..4] (and a k = 19 twin of the headline): one flat row each
+  cli           (--full) the kmerust command line on S10M and S100M FASTQ files: wall seconds
 The FULL report (every sub-result's roofline, phase walls, samples, explanations) goes to gpurun_out/bench_full.json
 (BENCH_FULL_PATH overrides) and, as a pointer, `full_report` in the line.
 
@@ -65,7 +71,7 @@ def parse_args():
     ap.add_argument("--capacity-hint", type=int, default=0, help="expected distinct k-mers per GPU (0 = estimate)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
-    ap.add_argument("--verify", action="store_true", help="(default at N = 1) check a 1/1024 key sample against the CPU oracle")
+    ap.add_argument("--verify", action="store_true", help="(default at N = 1 with --full) check a 1/1024 key sample against the CPU oracle")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--group", type=int, default=0,
                     help="N thread ranks on ONE device through kh_group_create / kh_group_merge (the N > 1 accounting on a 1-GPU box)")
@@ -76,7 +82,17 @@ def parse_args():
     ap.add_argument("--hg", action="store_true", help="run configs[4] alone (hg-shaped FASTA text -> histogram): for profiling that workload")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the end-to-end (host buffers in, results out) figures and the configs sub-results")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle check, the CPU baseline, the end-to-end figures, the other configurations, the "
+                         "command-line leg and (N > 1) the same-share and conservation figures; a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; see dump_outputs())")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.group > 1 or args.hg):
+        ap.error("--dump-outputs writes the outputs of the headline step: not with --group or --hg")
+    return args
 
 
 HINT_SOURCE = ("estimate_distinct(): genome length + reads x 150/256 substitutions x k (L-k+1)/L novel k-mers each x 0.92 -- an a-priori "
@@ -253,6 +269,35 @@ def verify_reads(dc, st, host, hq, k, min_quality):
             "what": "every key with mix(key) & 1023 == 0: exact count equality, plus the k-mer total (CPU oracle scan_flat; "
                     "vs krust only through that restatement -- the reference's own vectors are <= 32 bases, DESIGN.md section 2)",
             "cpu_seconds": time.perf_counter() - t0}
+
+
+DUMP_SAMPLE_READS = 2048
+
+
+def dump_outputs(path, dc, st, tb, tq, reads, k, min_quality, torch):
+    """--dump-outputs DIR: what the caller of the timed step receives after the last one, as float64 .npy files (so that two builds
+    can be compared output for output; the inputs are the seeded reads, the same for the same arguments):
+      stats.npy          [k-mers, distinct keys] of kh_finish
+      histogram.npy      (n, 2): count, number of keys with that count (kh_histogram: the whole table)
+      sample_keys.npy    (m, 2): high and low 32 bits of every distinct canonical key of DUMP_SAMPLE_READS reads drawn with SEED
+      sample_counts.npy  (m,): the table's count of each of those keys (kh_lookup; N > 1: rank 0's shard, 0 for keys it does not own)
+    The oracle only enumerates which keys to look up; every count comes from the table.  A few MB in all."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "stats.npy"), np.array([st["kmers"], st["distinct"]], dtype=np.float64))
+    np.save(os.path.join(path, "histogram.npy"), np.array(dc.histogram(), dtype=np.float64).reshape(-1, 2))
+    stride = READ_LEN + 1
+    rows = np.sort(np.random.default_rng(SEED).choice(reads, size=min(reads, DUMP_SAMPLE_READS), replace=False))
+    idx = torch.from_numpy(rows.astype(np.int64)).to(tb.device)
+    sb = tb.view(reads, stride)[idx].cpu().numpy().reshape(-1)
+    sq = tq.view(reads, stride)[idx].cpu().numpy().reshape(-1) if tq is not None else None
+    m = O.OracleMap()
+    m.process(sb, k, qual=sq, min_quality=min_quality)
+    keys, _ = m.arrays()
+    np.save(os.path.join(path, "sample_keys.npy"), np.stack([keys >> np.uint64(32), keys & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64))
+    np.save(os.path.join(path, "sample_counts.npy"), dc.lookup(keys).astype(np.float64))
 
 
 def measured_traffic(rf, reads, k, min_quality):
@@ -760,7 +805,7 @@ def main_group(args):
         st = sts[0]
         rf = roofline_of(st, nbytes * (2 if with_qual else 1), st["count_kernel_ms"], st["stage_ms"], k)
         verify = None
-        if not args.no_verify and reads <= 20_000_000:
+        if (args.full or args.verify) and not args.no_verify and reads <= 20_000_000:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O
             tot = 0
@@ -828,7 +873,7 @@ def main():
     if args.hg:   # configs[4] alone, as the headline of this invocation (profiling runs; the default line carries it as a sub-result)
         sub = None
         for _ in range(max(1, args.steps)):
-            sub = sub_config_hg(krust_amd, torch, dev, local_rank, verify=not args.no_verify)
+            sub = sub_config_hg(krust_amd, torch, dev, local_rank, verify=(args.full or args.verify) and not args.no_verify)
         out = {"metric": "canonical k-mers/s, hg-shaped FASTA text -> histogram (BASELINE configs[4])", "value": sub["value"], "unit": "k-mers/s", "n_gpus": 1,
                "steps": 1, "warmup": 1, "ms_per_step": sub["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
                "data": "synthetic", "config": {"workload": sub["workload"], "k": sub["k"], "reads_per_gpu": 0, "kmers_per_step_per_gpu": sub["kmers_per_step"],
@@ -915,7 +960,10 @@ def main():
             stage_ms[name] = stage_ms.get(name, 0.0) + ms
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # (before anything below resets the table)
+        dump_outputs(args.dump_outputs, dc, st, tb, tq, reads, k, args.min_quality, torch)
     per_rank = None
+    same_share = None
     if merged:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -923,13 +971,14 @@ def main():
         km = torch.tensor([st["kmers"]], dtype=torch.int64, device=cdev)
         dist.all_reduce(km, op=dist.ReduceOp.SUM)
         total_kmers = int(km.item())
-        # conservation across the merge (outside the timed region): the key-sharded tables together hold
-        # every occurrence exactly once, and the shards' key sets are disjoint by construction
-        hist = dc.histogram()
-        chk = torch.tensor([sum(c * f for c, f in hist), sum(f for _, f in hist)], dtype=torch.int64, device=cdev)
-        dist.all_reduce(chk, op=dist.ReduceOp.SUM)
-        mg = dict(mg, merged_occurrences=int(chk[0].item()), merged_distinct=int(chk[1].item()),
-                  conserved=bool(int(chk[0].item()) == total_kmers))
+        if args.full:
+            # conservation across the merge (outside the timed region): the key-sharded tables together hold
+            # every occurrence exactly once, and the shards' key sets are disjoint by construction
+            hist = dc.histogram()
+            chk = torch.tensor([sum(c * f for c, f in hist), sum(f for _, f in hist)], dtype=torch.int64, device=cdev)
+            dist.all_reduce(chk, op=dist.ReduceOp.SUM)
+            mg = dict(mg, merged_occurrences=int(chk[0].item()), merged_distinct=int(chk[1].item()),
+                      conserved=bool(int(chk[0].item()) == total_kmers))
         # the world RCCL itself reports (ncclCommCount inside the library) must be the world this run was launched with
         if merge_impl == "c" and mg.get("rccl_nranks") != world:
             raise RuntimeError(f"RCCL saw {mg.get('rccl_nranks')} ranks, the launcher {world}")
@@ -947,24 +996,23 @@ def main():
         # The same share on ONE GPU, measured in this run: the rank's own reads counted with no merge (reset + push + finish),
         # all ranks at once, rank 0's wall time.  The driver's N = 1 point is S100M (100 M reads); this is the N = 1 point of THIS
         # workload (125 M reads per GPU), so that a 1 -> N curve can be read without mixing the two.
-        same_share = None
-        fence()
-        t1 = time.perf_counter()
-        for _ in range(2):
-            dc.reset()
-            dc.push_device(tb.data_ptr(), tq.data_ptr() if with_qual else None, nbytes)
-            st1 = dc.finish()
-        torch.cuda.synchronize()
-        dt1 = (time.perf_counter() - t1) / 2
-        same_share = {"value": st1["kmers"] / dt1, "ms_per_step": dt1 * 1e3, "steps": 2, "kernel_ms_per_step": st1["count_kernel_ms"],
-                      "what": "rank 0's share counted alone on its GPU (no merge), measured after the timed loop of this run"}
-        fence()
+        if args.full:
+            fence()
+            t1 = time.perf_counter()
+            for _ in range(2):
+                dc.reset()
+                dc.push_device(tb.data_ptr(), tq.data_ptr() if with_qual else None, nbytes)
+                st1 = dc.finish()
+            torch.cuda.synchronize()
+            dt1 = (time.perf_counter() - t1) / 2
+            same_share = {"value": st1["kmers"] / dt1, "ms_per_step": dt1 * 1e3, "steps": 2, "kernel_ms_per_step": st1["count_kernel_ms"],
+                          "what": "rank 0's share counted alone on its GPU (no merge), measured after the timed loop of this run"}
+            fence()
     else:
         total_kmers = int(st["kmers"])
-        same_share = None
 
     verify = None
-    do_verify = (args.verify or (not merged and not args.no_verify))
+    do_verify = (args.verify or (args.full and not merged and not args.no_verify))
     if do_verify and rank == 0:
         host = tb.cpu().numpy()
         hq = tq.cpu().numpy() if with_qual else None
@@ -1034,12 +1082,12 @@ def main():
             out["config"]["single_gpu_same_share"] = same_share
         if verify is not None:
             out["verify"] = verify
-        if not merged and not args.no_cpu_baseline:
+        if args.full and not merged and not args.no_cpu_baseline:
             sample_reads = min(reads, 6_000_000)
             host = tb[: sample_reads * stride].cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(host, k, args.cpu_seconds)
             del host
-        if not merged and not args.no_extras:
+        if args.full and not merged and not args.no_extras:
             try:
                 out["end_to_end"] = end_to_end(dc, tb, torch, k)
             except Exception as e:  # (never lose the headline line over an extra)

@@ -172,10 +172,10 @@ def test_the_contract_line_of_a_full_report_fits_the_drivers_tail():
 
 @pytest.mark.gpu
 def test_bench_prints_one_small_line_and_a_full_report(tmp_path):
-    """The same on a real (reduced) run: `bench.py --reads 2000000` prints exactly ONE stdout line of <= 6 KB with every contract
+    """The same on a real (reduced) run: `bench.py --reads 2000000 --full` prints exactly ONE stdout line of <= 6 KB with every contract
     key, and the full report lands in the side file."""
     path = str(tmp_path / "full.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2000000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, BENCH_FULL_PATH=path, BENCH_CLI_PAUSE_S="0.3"))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

@@ -130,7 +130,7 @@ def test_bench_multi_rank_code_path_on_one_gpu():
     env = dict(os.environ, BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "2000000", "--no-cpu-baseline"],
+                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "2000000", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -144,13 +144,14 @@ def test_bench_multi_rank_code_path_on_one_gpu():
 
 
 @pytest.mark.parametrize("n", [2, 4])
-def test_bench_group_mode_runs_the_multi_rank_accounting_through_the_c_abi(n):
+def test_bench_group_mode_runs_the_multi_rank_accounting_through_the_c_abi(n, tmp_path):
     """RCCL refuses two ranks on one device, so the bench's C-ABI merge branch cannot run under torchrun on
     a 1-GPU box.  `bench.py --group N` drives N thread ranks through kh_group_create / kh_group_merge (the in-process hub) and
     fills the same config.merge / per_rank / conserved / rccl_nranks fields: the accounting code of the 8-GPU line runs here."""
     import json
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--group", str(n), "--steps", "2", "--warmup", "1", "--reads", "1000000"],
-                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, BENCH_FULL_PATH=f"/tmp/bench_group{n}.json"))
+    path = str(tmp_path / f"bench_group{n}.json")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--group", str(n), "--steps", "2", "--warmup", "1", "--reads", "1000000", "--full"],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, BENCH_FULL_PATH=path))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and len(lines[0]) <= 6144          # ONE line, and one the driver's 8 KB tail holds whole
@@ -160,17 +161,18 @@ def test_bench_group_mode_runs_the_multi_rank_accounting_through_the_c_abi(n):
     assert mg["path"].startswith("regions") and mg["merged_occurrences"] == n * d["config"]["kmers_per_step_per_gpu"] or mg["conserved"]
     assert len(d["config"]["per_rank"]) == n and d["config"]["per_rank_columns"][0] == "rank"
     assert d["verify"]["ok"] is True and d["config"]["mode"] == f"group{n}"
-    full = json.load(open(f"/tmp/bench_group{n}.json"))
+    full = json.load(open(path))
     assert full["config"]["merge"]["sent_count_sum"] > 0 and len(full["config"]["per_rank"]) == n
 
 
-def test_bench_force_merge_drives_the_rccl_merge_on_one_gpu():
+def test_bench_force_merge_drives_the_rccl_merge_on_one_gpu(tmp_path):
     """`bench.py --force-merge`: the N > 1 step -- count, then kh_merge_across over a REAL RCCL communicator (of one rank) inside
     the timed region -- with every key of the N > 1 line (config.merge from the library, rccl_nranks from ncclCommCount,
     conservation, per_rank, single_gpu_same_share): what a torchrun launch on 8 GPUs executes, on the box's one."""
     import json
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-merge", "--steps", "2", "--warmup", "1", "--reads", "1500000", "--verify"],
-                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, BENCH_FULL_PATH="/tmp/bench_force_merge.json"))
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-merge", "--steps", "2", "--warmup", "1", "--reads", "1500000", "--verify",
+                          "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                         env=dict(os.environ, BENCH_FULL_PATH=str(tmp_path / "bench_force_merge.json")))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and len(lines[0]) <= 6144
