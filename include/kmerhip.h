@@ -222,7 +222,9 @@ int kh_export_regions_device(kh_ctx *ctx, uint32_t nparts, uint64_t *d_keys, uin
                              uint64_t *table_regions);
 /* d_keys[s], d_counts[s]: sender s's pairs for THIS shard (device pointers, host arrays of nsenders
  * entries); d_region_counts[s]: sender s's live counts of the sender_regions / shard_count regions of
- * this shard's range. */
+ * this shard's range.  A sender whose region counts are all zero is never dereferenced: its key /
+ * count pointers may be anything, NULL included (d_region_counts[s] must stay valid).  The same
+ * holds for the packed and heads variants below. */
 int kh_merge_regions_device(kh_ctx *ctx, uint32_t nsenders, uint64_t sender_regions,
                             const uint64_t *const *d_keys, const uint64_t *const *d_counts,
                             const uint32_t *const *d_region_counts);

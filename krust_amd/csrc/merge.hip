@@ -524,8 +524,12 @@ int merge_regions(kh_ctx *c, int fmt, uint32_t nsenders, uint64_t sender_regions
     for (u64 q = nregions; q > nr; q >>= 1) ++a.dshift;
     for (u64 q = nr; q > nregions; q >>= 1) --a.dshift;
     for (uint32_t s = 0; s < nsenders; ++s) {
-        a.src[s].keys = (const u64 *)d_keys[s];
-        a.src[s].counts = packed ? nullptr : (const u64 *)d_counts[s];
+        // A sender without units is never read: whatever pointer it came with (NULL, a stale one, one past the end of a receive
+        // buffer) is replaced by memory of this context's own.  shard_merge_narrow_kernel's branch-free prefetch loads unit 0 of
+        // a sender whose segment is empty and drops the value; this makes that load harmless whatever the caller passed.
+        const bool none = totals[s] == 0;
+        a.src[s].keys = none ? (const u64 *)c->merge_off : (const u64 *)d_keys[s];
+        a.src[s].counts = packed ? nullptr : (none ? (const u64 *)c->merge_off : (const u64 *)d_counts[s]);
         a.src[s].off = c->merge_off + (u64)s * (nr + 1);
     }
     a.sgeo = sgeo;
@@ -637,12 +641,27 @@ int merge_regions(kh_ctx *c, int fmt, uint32_t nsenders, uint64_t sender_regions
     }
     rc = sync_counters(c);
     if (rc != KH_OK) return rc;
-    if (c->h_ctr->part_failed) {  // some target regions overflowed: grow, then insert their pairs directly
+    if (c->h_ctr->part_failed) {  // some target regions failed: insert their pairs directly, into a larger table if one was full
         const kh::RegionGeom old_geo{tg.p1_bits, tg.b2};
+        // code 1: the region is full; code 2 (8-byte image only): a count left 32 bits, the region itself has room (as batch.hip
+        // finish_batch tells them apart)
+        std::vector<uint8_t> hf(nwin);
+        HIP_TRY(c, hipMemcpy(hf.data(), c->rfail + region0, nwin, hipMemcpyDeviceToHost));
+        bool any_full = false, any_count = false;
+        for (u64 r = 0; r < nwin; ++r) {
+            any_full |= hf[r] == 1;
+            any_count |= hf[r] == 2;
+        }
+        if (any_count) c->narrow_banned = true;
+        if (c->trace)
+            fprintf(stderr, any_full ? "[kmerhip] merge: %llu target regions overflowed: growing and re-inserting them directly\n"
+                                     : "[kmerhip] merge: a count left 32 bits in %llu target regions: 16-byte table from here on, re-inserting them directly\n",
+                    (u64)c->h_ctr->part_failed);
         StageTimer t(c, ST_GROW);
-        rc = close_fresh_window(c);  // growing rehashes the whole table
+        rc = close_fresh_window(c);  // growing rehashes the whole table, widening reads all of the image
         if (rc != KH_OK) return rc;
-        rc = grow_to(c, c->cap * 2);
+        if (any_full) rc = grow_to(c, c->cap * 2);
+        else rc = ensure_wide(c);  // (nothing was full: the table keeps its size, the re-insert goes through the 16-byte form)
         if (rc != KH_OK) return rc;
 #define KH_MERGE_DIRECT(FMT) \
     hipLaunchKernelGGL((kh::shard_merge_kernel<false, true, FMT>), dim3((unsigned)nwin), dim3(1024), 0, c->stream, \

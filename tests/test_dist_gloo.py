@@ -21,10 +21,17 @@ from krust_amd.distributed import shard_range, exchange_pairs, group_pairs_by_ow
 
 dist.init_process_group("gloo")
 rank, world = dist.get_rank(), dist.get_world_size()
-N_READS, K, SEED = 6000, 21, 20260130
+N_READS, K, SEED = int(os.environ.get("KH_TEST_N_READS", "6000")), 21, 20260130
 lo, hi = shard_range(N_READS, rank, world)
 bases, _ = O.synth_reads(SEED, 1 << 15, 150, lo, hi - lo, with_qual=False)
-m = O.OracleMap(); m.scan_flat(bases, K)
+m = O.OracleMap()
+if hi > lo:
+    m.scan_flat(bases, K)
+if N_READS < world:  # (a lopsided run: world - N_READS ranks were given nothing)
+    assert (len(m) == 0) == (hi == lo)
+    empties = [None] * world
+    dist.all_gather_object(empties, len(m) == 0)
+    assert sum(empties) == world - N_READS, empties
 keys, cnts = m.arrays()
 gk, gc, parts = group_pairs_by_owner(keys, cnts, world, lambda key, w: krust_amd.owner(key, K, w))
 rk, rc = exchange_pairs(torch.from_numpy(gk.view(np.int64).copy()), torch.from_numpy(gc.view(np.int64).copy()), parts.tolist())
@@ -49,17 +56,26 @@ dist.destroy_process_group()
 '''
 
 
-@pytest.mark.parametrize("world", [2, 3])
-def test_gloo_sharded_merge(world, tmp_path):
+def _run_worker(world, n_reads, tmp_path, port):
     script = tmp_path / "worker.py"
     script.write_text(f"ROOT = {ROOT!r}\n" + WORKER)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    port = 29600 + world + (os.getpid() % 200)
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", KH_TEST_N_READS=str(n_reads))
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), str(script)],
                          capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert f"DIST_OK {world}" in out.stdout
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_gloo_sharded_merge(world, tmp_path):
+    _run_worker(world, 6000, tmp_path, 29600 + world + (os.getpid() % 200))
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_gloo_sharded_merge_of_a_single_read(world, tmp_path):
+    """N_READS = 1: shard_range gives world - 1 ranks nothing; the same assertions."""
+    _run_worker(world, 1, tmp_path, 29610 + world + (os.getpid() % 200))
 
 
 # merge_across_ranks itself (format vote, region-ordered export, the pipeline over pieces of the region
@@ -192,16 +208,25 @@ import datetime
 dist.init_process_group("gloo", timeout=datetime.timedelta(seconds=60))
 rank, world = dist.get_rank(), dist.get_world_size()
 N_READS, K, SEED, RBITS = 4000, 19, 20260130, 11
-lo, hi = shard_range(N_READS, rank, world)
+# KH_TEST_LOAD: "spread" = every rank counts its shard_range of the reads; "first" / "last" = that rank holds the whole
+# table and every other rank an empty one (what the product's 128 MiB chunks make of a small input)
+LOAD = os.environ.get("KH_TEST_LOAD", "spread")
+holder = {"spread": None, "first": 0, "last": world - 1}[LOAD]
+lo, hi = shard_range(N_READS, rank, world) if holder is None else ((0, N_READS) if rank == holder else (0, 0))
 bases, _ = O.synth_reads(SEED, 1 << 14, 150, lo, hi - lo, with_qual=False)
-m = O.OracleMap(); m.scan_flat(bases, K)
+m = O.OracleMap()
+if hi > lo:
+    m.scan_flat(bases, K)
+assert (len(m) == 0) == (holder is not None and rank != holder)
+heavy = 0 if holder is None else holder  # the rank whose counts are raised in the large-counts leg
 full_b, _ = O.synth_reads(SEED, 1 << 14, 150, 0, N_READS, with_qual=False)
 full = O.OracleMap(); full.scan_flat(full_b, K)
 for pieces, path in ((1, "regions-heads"), (None, "regions-heads-x4"), (2, "regions-heads-x2")):
     c = StandIn(K, RBITS)
     c.table = dict(m.as_dict())
-    c.table[next(iter(c.table))] += 5000  # one count that needs several heads
-    bumped = next(iter(c.table))
+    bumped = next(iter(c.table)) if c.table else None
+    if c.table:
+        c.table[bumped] += 5000  # one count that needs several heads
     info = merge_across_ranks(c, pieces=pieces, phase_times=True)
     assert info["path"] == path, info
     assert all(krust_amd.owner(key, K, world) == rank for key in c.table)
@@ -212,7 +237,8 @@ for pieces, path in ((1, "regions-heads"), (None, "regions-heads-x4"), (2, "regi
         for tab, b in gathered:
             assert not (set(tab) & set(union))
             union.update(tab)
-            want[b] += 5000
+            if b is not None:
+                want[b] += 5000
         assert union == want, "merged shards differ from the single-process result"
 # A table whose counts need more heads than the send buffer holds (> 2 per key on average): piece 0 alone
 # would fit, so only the up-front size check can tell -- every rank must then leave the pipeline TOGETHER and
@@ -220,19 +246,22 @@ for pieces, path in ((1, "regions-heads"), (None, "regions-heads-x4"), (2, "regi
 # and the region window must be back to (0, 1) afterwards.
 c = StandIn(K, RBITS)
 c.allow_packed = True
-c.table = {key: cnt + 100 for key, cnt in m.as_dict().items()} if rank == 0 else dict(m.as_dict())
+c.table = {key: cnt + 100 for key, cnt in m.as_dict().items()} if rank == heavy else dict(m.as_dict())
 info = merge_across_ranks(c, pieces=None, phase_times=False)
 assert info["path"] == "regions-packed", info
 assert c.win == (0, 1)
 gathered = [None] * world
-dist.all_gather_object(gathered, (c.table, len(m) if rank == 0 else 0))
+dist.all_gather_object(gathered, (c.table, len(m) if rank == heavy else 0))
 if rank == 0:
     union = {}
     for tab, _ in gathered:
         assert not (set(tab) & set(union))
         union.update(tab)
-    assert sum(union.values()) == full.total() + 100 * len(m) and set(union) == set(full.as_dict())
+    assert sum(union.values()) == full.total() + 100 * sum(n for _, n in gathered) and set(union) == set(full.as_dict())
 sys.stdout.write(f"PIPE_OK {world}\n"); sys.stdout.flush()
+if holder is not None:  # (the liveness leg below does not depend on who holds what: it runs in the balanced variant)
+    dist.destroy_process_group()
+    raise SystemExit(0)
 # ---- liveness: a rank that fails on its own takes EVERY rank out of the same merge, nobody hangs ----
 # (VERDICT r2 next-1c.)  One rank's stand-in raises at a named call -- the export of a later piece (one transfer
 # already in flight), the up-front unit counts, the merge of a piece, the very first finish, the one-shot export --
@@ -282,18 +311,30 @@ dist.destroy_process_group()
 '''
 
 
-@pytest.mark.parametrize("world", [2, 4])
-def test_gloo_merge_across_ranks_pipeline_with_cpu_standin(world, tmp_path):
+def _run_standin(world, tmp_path, load, port):
     script = tmp_path / "standin.py"
     script.write_text(f"ROOT = {ROOT!r}\n" + STANDIN)
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    port = 29650 + world + (os.getpid() % 200)
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", KH_TEST_LOAD=load)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), str(script)],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert out.stdout.count(f"PIPE_OK {world}") == world
+    return out
+
+
+@pytest.mark.parametrize("world", [2, 4])
+def test_gloo_merge_across_ranks_pipeline_with_cpu_standin(world, tmp_path):
+    out = _run_standin(world, tmp_path, "spread", 29650 + world + (os.getpid() % 200))
     assert out.stdout.count(f"FAULT_OK {world}") == world   # the failure-injection leg: every rank out of every failed merge
+
+
+@pytest.mark.parametrize("load", ["first", "last"])
+@pytest.mark.parametrize("world", [2, 4])
+def test_gloo_merge_across_ranks_when_one_rank_holds_the_whole_table(world, load, tmp_path):
+    """The same merge legs (heads in one shot and in pieces, the large-counts packed route) with every rank but the
+    first / the last holding an EMPTY table: the same assertions as the balanced legs."""
+    _run_standin(world, tmp_path, load, 29660 + world + (os.getpid() % 200) + (10 if load == "last" else 0))
 
 
 def test_shard_range_partition():

@@ -317,6 +317,63 @@ def test_cli_on_several_ranks_equals_one_gpu(tmp_path, devices):
     assert a.returncode == 0 and tsv(a.stdout) == tsv(b)
 
 
+def _records(path):
+    """(records, quals or None) of a FASTA / 4-line FASTQ file, for the oracle."""
+    lines = open(path, "rb").read().split(b"\n")
+    if lines and lines[0].startswith(b"@"):
+        return lines[1::4][:len(lines) // 4], lines[3::4][:len(lines) // 4]
+    recs = []
+    for l in lines:
+        if l.startswith(b">"):
+            recs.append(b"")
+        elif recs:
+            recs[-1] += l
+    return recs, None
+
+
+@pytest.mark.parametrize("devices", ["0,0,0,0", "0,0,0"], ids=["4-ranks", "3-ranks-pairs-route"])
+def test_cli_on_several_ranks_with_the_default_chunking(tmp_path, devices):
+    """WITHOUT KMERUST_TEXT_CHUNK_KB: the product's 128 MiB chunks go to the ranks in turn, so these inputs -- a few MB of
+    FASTQ (one chunk), a FASTA with fewer records than ranks, an empty file, a FASTQ that -Q masks entirely -- leave ranks
+    with an EMPTY table at the merge.  Output == the one-device output == the oracle's, exit status 0, nothing more on stderr.
+    That ranks were empty is read from the run itself: KMERUST_TIMING reports the number of chunks handed out (rank i gets
+    chunks i, i + W, ...: fewer chunks than ranks leaves the ranks behind them without input)."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    assert "KMERUST_TEXT_CHUNK_KB" not in os.environ
+    nranks = devices.count(",") + 1
+    fq, _ = _write_reads(tmp_path)
+    empty = tmp_path / "empty.fa"
+    empty.write_bytes(b"")
+    masked = tmp_path / "masked.fq"
+    recs, _ = _records(fq)
+    masked.write_bytes(b"".join(b"@m%d\n%s\n+\n%s\n" % (i, r, b"!" * len(r)) for i, r in enumerate(recs[:500])))
+    cases = [(21, fq, []), (21, fq, ["-Q", "20"]), (3, fx("simple.fa"), []), (21, str(empty), []), (21, str(masked), ["-Q", "20"])]
+    timing = {"KMERUST_TIMING": "1"}
+    plain = lambda err: [l for l in err.splitlines() if b"kmerust_timing" not in l]
+    for k, path, extra in cases:
+        assert os.path.getsize(path) < 128 << 20
+        recs, quals = _records(path)
+        m = O.count_records(recs, k, quals=quals if extra else None, min_quality=int(extra[1]) if extra else None)
+        args = [str(k), path, *extra, "--quiet"]
+        one = run(*args, "--format", "tsv", env=timing)
+        many = run(*args, "--format", "tsv", "--devices", devices, env=timing)
+        assert one.returncode == 0 and many.returncode == 0, (path, one.stderr, many.stderr)
+        assert plain(many.stderr) == plain(one.stderr), (path, many.stderr)
+        t = json.loads([l for l in many.stderr.splitlines() if b"kmerust_timing" in l][-1])["kmerust_timing"]
+        assert t["chunks"] < nranks, (path, t)                      # at least one rank really had no input
+        assert sorted(many.stdout.splitlines()) == sorted(one.stdout.splitlines())
+        assert tsv(many.stdout) == m.as_str_dict(k) and len(many.stdout.splitlines()) == len(m)
+        if str(masked) == path or str(empty) == path:
+            assert len(m) == 0 and many.stdout == b""
+        h1 = run(*args, "--format", "histogram")
+        hn = run(*args, "--format", "histogram", "--devices", devices)
+        assert h1.returncode == 0 and hn.returncode == 0 and hn.stderr == h1.stderr, (path, hn.stderr)
+        assert hn.stdout == h1.stdout
+        assert [tuple(map(int, l.split(b"\t"))) for l in hn.stdout.splitlines()] == m.histogram(1)
+
+
 def test_gpus_flag_validation():
     r = run("21", fx("simple.fa"), "--gpus", "0")
     assert r.returncode == 2 and b"at least one GPU" in r.stderr
