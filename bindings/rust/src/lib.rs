@@ -98,6 +98,12 @@ pub mod sys {
         pub fn kh_histogram(ctx: *mut KhCtx, min_count: u64, count: *mut u64, freq: *mut u64,
                             cap: u64, n: *mut u64) -> c_int;
         pub fn kh_lookup(ctx: *mut KhCtx, keys: *const u64, n: u64, counts: *mut u64) -> c_int;
+        /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
+        pub fn kh_result_text_begin(ctx: *mut KhCtx, format: u32, min_count: u64, n_records: *mut u64,
+                                    n_bytes: *mut u64) -> c_int;
+        /// whole records, at most `cap` bytes; `*n == 0`: the stream has ended; -8 (KH_ERR_RANGE): cap < the next record
+        pub fn kh_result_text_next(ctx: *mut KhCtx, buf: *mut u8, cap: u64, n: *mut u64) -> c_int;
+        pub fn kh_result_text_next_device(ctx: *mut KhCtx, d_buf: *mut u8, cap: u64, n: *mut u64) -> c_int;
         // host memory the device reaches by DMA (no staging copy in kh_push / kh_push_text / kh_result_copy)
         pub fn kh_host_alloc(out: *mut *mut c_void, bytes: u64) -> c_int;
         pub fn kh_host_free(p: *mut c_void) -> c_int;
@@ -132,6 +138,15 @@ pub enum HipError {
 
 /// `KMERHIP_ABI_VERSION` of the `include/kmerhip.h` that `mod sys` mirrors: the structs above are laid out for it.
 pub const ABI_VERSION: c_int = 2;
+
+/// The record formats of `kh_result_text_begin` (`KH_OUT_*`): the reference's `OutputFormat` without the histogram.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(u32)]
+pub enum TextFormat {
+    Fasta = 1,
+    Tsv = 2,
+    Json = 3,
+}
 
 /// Called before the first `kh_create` of every constructor: a library of another ABI version is refused, not guessed at.
 fn check_abi() -> Result<(), HipError> {
@@ -321,6 +336,28 @@ impl HipKmerMap {
             sys::kh_result_copy(self.ctx, keys.as_mut_ptr(), counts.as_mut_ptr(), n, min_count, &mut got)
         })?;
         Ok(keys.into_iter().zip(counts).take(got as usize).collect())
+    }
+
+    /// `output_counts` (`src/run.rs:441-486`) for the fasta / tsv / json formats: the records are unpacked, their counts
+    /// printed and the JSON document framed ON THE DEVICE; `w` receives the text in pieces of whole records, in table
+    /// order.  Returns (records, bytes) written.  The table stays as it is (`&mut self`: the stream is state of the context).
+    pub fn write_text<W: std::io::Write>(&mut self, format: TextFormat, min_count: u64, w: &mut W) -> Result<(u64, u64), HipError> {
+        check(self.ctx, unsafe { sys::kh_finish(self.ctx, std::ptr::null_mut()) })?;
+        let (mut n_records, mut n_bytes) = (0u64, 0u64);
+        check(self.ctx, unsafe { sys::kh_result_text_begin(self.ctx, format as u32, min_count, &mut n_records, &mut n_bytes) })?;
+        let mut piece = vec![0u8; (n_bytes.min(8 << 20) as usize).max(128)];
+        let mut written = 0u64;
+        loop {
+            let mut n = 0u64;
+            check(self.ctx, unsafe { sys::kh_result_text_next(self.ctx, piece.as_mut_ptr(), piece.len() as u64, &mut n) })?;
+            if n == 0 {
+                break;
+            }
+            w.write_all(&piece[..n as usize]).map_err(|e| HipError::Device(format!("writing the text failed: {e}")))?;
+            written += n;
+        }
+        debug_assert_eq!(written, n_bytes);
+        Ok((n_records, written))
     }
 
     /// `KmerMap::into_hashmap` (`src/run.rs:573-582`).

@@ -193,6 +193,35 @@ int kh_result_copy(kh_ctx *ctx, uint64_t *keys, uint64_t *counts, uint64_t cap,
 /* Same into device arrays (for the multi-GPU exchange and device consumers). */
 int kh_result_copy_device(kh_ctx *ctx, uint64_t *d_keys, uint64_t *d_counts, uint64_t cap,
                           uint64_t min_count, uint64_t *n);
+/* The same result as TEXT, formatted on the device: replaces output_counts (src/run.rs:441-486) -- unpacking, the decimal
+ * counts and the framing happen in HBM, and only text crosses the link.  Three formats, byte for byte the reference's:
+ *   KH_OUT_FASTA  >{count}\n{kmer}\n          KH_OUT_TSV  {kmer}\t{count}\n
+ *   KH_OUT_JSON   serde_json's pretty form of [{"kmer": .., "count": ..}, ..]: the COMPLETE document, brackets included
+ *                 ("[]\n" when there is no record)
+ * A pull interface, because the text can be larger than any one buffer: kh_result_text_begin sizes the stream
+ * (*n_records, *n_bytes: its totals, either may be NULL), every kh_result_text_next* hands out the next piece --
+ * WHOLE records, at most cap bytes -- and *n = 0 with KH_OK says that the stream has ended.
+ *   - Records come in table-slot order; the same table gives the same bytes on every run, and the concatenation of the
+ *     pieces is the same document for EVERY sequence of cap values.
+ *   - JSON: the opening "[\n" belongs to the first record; the closing "\n]\n" follows the last record in the same piece
+ *     when it fits there, else it is a piece of its own.
+ *   - A cap smaller than the next record: KH_ERR_RANGE, nothing is consumed (call again with more room).
+ *   - next without begin: KH_ERR_STATE.  So is next after any call that entered the context for something else than
+ *     reading -- every kh_push*, kh_reset, kh_merge_*, kh_set_shard, the exports, kh_result_copy (which takes the same
+ *     scratch memory): begin again.  kh_result_size, kh_lookup, kh_histogram and kh_finish may be interleaved.
+ *   - begin on a running stream restarts it.  Shard tables (kh_set_shard / kh_merge_across) stream like full ones.
+ *   - kh_result_text_next takes pageable memory, or -- faster: no bounce -- memory of kh_host_alloc / kh_host_register;
+ *     the next range of the table is formatted while the current one travels.  kh_result_text_next_device writes
+ *     device memory of this context's device (any alignment) and returns when it is complete.
+ *   - Give cap room: the device formats up to 64 MiB at a time, and a call whose cap ends inside such a chunk finds the
+ *     last record end with a small blocking read from the device -- correct for any cap, but a cap of a few records
+ *     costs a device round trip per call.  Pieces of 1 MiB and more run at the link's rate. */
+#define KH_OUT_FASTA 1
+#define KH_OUT_TSV 2
+#define KH_OUT_JSON 3
+int kh_result_text_begin(kh_ctx *ctx, uint32_t format, uint64_t min_count, uint64_t *n_records, uint64_t *n_bytes);
+int kh_result_text_next(kh_ctx *ctx, uint8_t *buf, uint64_t cap, uint64_t *n);
+int kh_result_text_next_device(kh_ctx *ctx, uint8_t *d_buf, uint64_t cap, uint64_t *n);
 /* Count-of-counts after the min_count filter, ascending by count
  * (compute_histogram, src/histogram.rs:88-94 as used by run.rs:471-481). */
 int kh_histogram(kh_ctx *ctx, uint64_t min_count, uint64_t *count, uint64_t *freq,

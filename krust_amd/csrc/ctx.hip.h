@@ -5,6 +5,7 @@
 //   batch.hip     counting one device-resident range: the direct path and the partitioned batch (level 1 -> level 2 -> regions)
 //   input.hip     kh_push* / kh_push_text*: staging, device accumulation, record scanning
 //   merge.hip     exports and merges of one context (pairs, dense, region-ordered)
+//   format.hip    kh_result_text_*: the table formatted as text on the device and streamed out in pieces
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
 //
@@ -281,6 +282,33 @@ struct kh_ctx {
     struct TxtHost { u64 total; u64 end_mark; uint32_t err; uint8_t first, last; } *h_txt = nullptr;  // pinned
     double text_ms = 0.0;
 
+    // ---- kh_result_text_*: the table as text, streamed in pieces (format.hip) ----
+    // begin sizes every tile of FMT_TILE slots (records, bytes) and scans both; next formats ranges of whole tiles into one of two
+    // device chunks -- the idle partition buffers where there are any, else small buffers of the stream's own -- and hands their text
+    // out record-aligned: chunk i + 1 is formatted on `stream` while chunk i travels on `cstream`.  `on` falls with every call
+    // that enters the context for anything but reading (enter(), reader = false).
+    struct TextStream {
+        bool on = false;
+        uint32_t format = 0;
+        u64 min_count = 0, ntiles = 0;
+        u64 n_records = 0, rec_bytes = 0;  // totals; rec_bytes without the document tail
+        u64 next_tile = 0;                 // first tile no chunk holds yet
+        bool tail_done = false;
+        std::vector<u64> toff;             // host copy of the tiles' byte offsets (ntiles + 1)
+        struct Chunk {
+            uint8_t *d = nullptr;
+            u64 cap = 0, len = 0, pos = 0;  // bytes it can hold / holds / has handed out
+            bool valid = false;
+            hipEvent_t done = nullptr;      // its formatting kernel (on `stream`)
+        } ch[2];
+        int cur = 0;                       // the chunk being handed out
+    } ts;
+    uint8_t *ts_own[2] = {nullptr, nullptr};  u64 ts_own_cap[2] = {0, 0};  // chunks of the stream's own (no partition buffers to use)
+    uint32_t *ts_trec = nullptr;  u64 ts_trec_cap = 0;   // per tile: records
+    uint32_t *ts_tbyt = nullptr;  u64 ts_tbyt_cap = 0;   // per tile: bytes
+    u64 *ts_roff = nullptr;       u64 ts_roff_cap = 0;   // exclusive scans of the two
+    u64 *ts_boff = nullptr;       u64 ts_boff_cap = 0;
+
     bool poisoned = false;
     std::string last_error;
 };
@@ -315,7 +343,9 @@ inline int grid_for(u64 items) {
 // ---- kmerhip.hip -----------------------------------------------------------------------------------------------------------
 // Every entry point starts with enter(): host pushes are accumulated on the device and counted lazily; anything that looks at
 // the table first counts what is pending.
-int enter(kh_ctx *c, bool flush_pending = true, bool need_table = true, bool keep_window = false, bool narrow_ok = false);
+// reader: the call only reads the table (a text stream in progress survives it: kh_result_text_next).
+int enter(kh_ctx *c, bool flush_pending = true, bool need_table = true, bool keep_window = false, bool narrow_ok = false,
+          bool reader = false);
 int need_table(kh_ctx *c);
 void resize_empty_table(kh_ctx *c, u64 newcap);
 int clear_if_dirty(kh_ctx *c);
@@ -348,7 +378,8 @@ int flush_acc(kh_ctx *c, bool carry);
 int flush_text(kh_ctx *c);
 int scan_unscanned(kh_ctx *c);
 bool is_pinned_host(const void *p);
-int d2h_staged(kh_ctx *c, void *dst, const void *d_src, u64 bytes);
+// ready: the event behind which d_src is complete (nullptr: it was produced on the compute stream, which is then drained)
+int d2h_staged(kh_ctx *c, void *dst, const void *d_src, u64 bytes, hipEvent_t ready = nullptr);
 // ---- merge.hip
 enum { XF_WIDE = 0, XF_PACKED64 = 1, XF_HEADS32 = 2 };  // exchange unit formats (shard.hip.h)
 int mark_touched_regions(kh_ctx *c, const void *ovf_list, const u64 *d_ovf, u64 ovf_lim);  // (batch.hip: before the overflow list's insert ...
@@ -363,6 +394,8 @@ int merge_regions(kh_ctx *c, int fmt, uint32_t nsenders, uint64_t sender_regions
                   const uint64_t *const *d_counts, const uint32_t *const *d_region_counts, u64 *d_digest = nullptr, bool *digest_done = nullptr);
 // ---- exchange.hip
 void comm_release(kh_ctx *c);
+// ---- format.hip
+void text_release(kh_ctx *c);  // kh_destroy: the text stream's buffers and events
 
 // ---- stage timing: HIP events on the launch stream, resolved lazily ---------------------------
 struct StageTimer {

@@ -84,12 +84,13 @@ int ensure_stage(kh_ctx *c, u64 need) {
 // Device -> pageable host memory through the two pinned staging buffers: the D2H of chunk i+1 runs
 // while chunk i is copied out (by several threads: first-touch page faults of a fresh destination
 // array cost more than the copy itself).
-int d2h_staged(kh_ctx *c, void *dst, const void *d_src, u64 bytes) {
+int d2h_staged(kh_ctx *c, void *dst, const void *d_src, u64 bytes, hipEvent_t ready) {
     const bool pinned_dst = is_pinned_host(dst);
     int rc = ensure_stage(c, pinned_dst ? 0 : (bytes + 1) / 2);
     if (rc != KH_OK) return rc;
     if (pinned_dst) {  // a registered destination takes the DMA itself: no bounce, no first-touch faults
-        HIP_TRY(c, hipStreamSynchronize(c->stream));  // d_src was produced on the compute stream
+        if (ready) HIP_TRY(c, hipStreamWaitEvent(c->cstream, ready, 0));  // (the compute stream goes on: it formats the next chunk)
+        else HIP_TRY(c, hipStreamSynchronize(c->stream));  // d_src was produced on the compute stream
         HIP_TRY(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, c->cstream));
         HIP_TRY(c, hipStreamSynchronize(c->cstream));
         return KH_OK;
@@ -101,7 +102,8 @@ int d2h_staged(kh_ctx *c, void *dst, const void *d_src, u64 bytes) {
         const uintptr_t hi = ((uintptr_t)dst + bytes) & ~(uintptr_t)((2u << 20) - 1);
         if (hi > lo) (void)madvise((void *)lo, hi - lo, MADV_HUGEPAGE);
     }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // d_src was produced on the compute stream
+    if (ready) HIP_TRY(c, hipEventSynchronize(ready));
+    else HIP_TRY(c, hipStreamSynchronize(c->stream));   // d_src was produced on the compute stream
     HIP_TRY(c, hipStreamSynchronize(c->cstream));  // the staging buffers are free
     const u64 CH = 2 * c->stage_bytes;
     const u64 nch = (bytes + CH - 1) / CH;

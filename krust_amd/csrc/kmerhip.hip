@@ -42,8 +42,9 @@ void read_knobs(Knobs &k) {
 #endif
 }
 
-int enter(kh_ctx *c, bool flush_pending, bool need_table, bool keep_window, bool narrow_ok) {
+int enter(kh_ctx *c, bool flush_pending, bool need_table, bool keep_window, bool narrow_ok, bool reader) {
     if (!c) return KH_ERR_BAD_ARG;
+    if (!reader) c->ts.on = false;  // (whatever may change the table, or takes the partition buffers, ends a text stream)
 #if KH_TESTING
     read_knobs(c->knobs);  // (tests flip the switches between calls on one context; the product library reads them once, at kh_create)
 #endif
@@ -532,6 +533,7 @@ extern "C" void kh_destroy(kh_ctx *c) {
     comm_release(c);
     drain_events(c);
     if (c->cstream) (void)hipStreamSynchronize(c->cstream);
+    text_release(c);
     for (int i = 0; i < 2; ++i) {
         if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
         if (c->acc[i]) (void)hipFree(c->acc[i]);
@@ -606,7 +608,7 @@ extern "C" int kh_reset(kh_ctx *c) {
 }
 
 extern "C" int kh_finish(kh_ctx *c, kh_stats *st) {
-    int rc = enter(c, true, true, false, true);
+    int rc = enter(c, true, true, false, true, true);
     if (rc != KH_OK) return rc;
     rc = sync_counters(c);
     if (rc != KH_OK) return rc;
@@ -657,7 +659,7 @@ int read_cursor(kh_ctx *c, u64 *cursor, u64 *big) {
 }  // namespace khi
 
 extern "C" int kh_result_size(kh_ctx *c, uint64_t min_count, uint64_t *n) {
-    int rc = enter(c, true, true, false, true);
+    int rc = enter(c, true, true, false, true, true);
     if (rc != KH_OK) return rc;
     if (!n) return fail(c, KH_ERR_BAD_ARG, "n is NULL");
     rc = zero_cursors(c);
@@ -747,7 +749,7 @@ extern "C" int kh_result_copy(kh_ctx *c, uint64_t *keys, uint64_t *counts, uint6
 
 extern "C" int kh_histogram(kh_ctx *c, uint64_t min_count, uint64_t *count, uint64_t *freq, uint64_t cap,
                             uint64_t *n) {
-    int rc = enter(c, true, true, false, true);
+    int rc = enter(c, true, true, false, true, true);
     if (rc != KH_OK) return rc;
     if (!n || (cap && (!count || !freq))) return fail(c, KH_ERR_BAD_ARG, "NULL output");
     u64 *d_dense = nullptr, *d_big = nullptr;
@@ -806,7 +808,7 @@ extern "C" int kh_histogram(kh_ctx *c, uint64_t min_count, uint64_t *count, uint
 }
 
 extern "C" int kh_lookup(kh_ctx *c, const uint64_t *keys, uint64_t n, uint64_t *counts) {
-    int rc = enter(c, true, true, false, true);
+    int rc = enter(c, true, true, false, true, true);
     if (rc != KH_OK) return rc;
     if (n == 0) return KH_OK;
     if (!keys || !counts) return fail(c, KH_ERR_BAD_ARG, "NULL argument");

@@ -237,9 +237,9 @@ int cli_main(int argc, char **argv) {
             const Timing &t = timing();
             const double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             fprintf(stderr, "{\"kmerust_timing\": {\"total_s\": %.6f, \"create_s\": %.6f, \"read_s\": %.6f, \"push_s\": %.6f, \"finish_s\": %.6f, "
-                            "\"result_s\": %.6f, \"write_s\": %.6f, \"buffers_s\": %.6f, \"destroy_s\": %.6f, \"bytes_read\": %llu, \"chunks\": %llu, \"device_record_scan\": %s}}\n",
+                            "\"result_s\": %.6f, \"write_s\": %.6f, \"buffers_s\": %.6f, \"destroy_s\": %.6f, \"bytes_read\": %llu, \"chunks\": %llu, \"device_record_scan\": %s, \"writer\": \"%s\"}}\n",
                     total, t.create_s, t.read_s, t.push_s, t.finish_s, t.result_s, t.write_s, t.buffers_s, t.destroy_s, (unsigned long long)t.bytes_read,
-                    (unsigned long long)t.chunks, t.text_path ? "true" : "false");
+                    (unsigned long long)t.chunks, t.text_path ? "true" : "false", t.device_writer ? "device" : "host");
         }
     } timing_printer{t_begin};
 #if defined(__has_feature)
@@ -255,15 +255,18 @@ int cli_main(int argc, char **argv) {
         kc.k(k).min_count(min_count).format(fmt).input_format(in_fmt).min_quality(min_quality).devices(devices);
         if (const char *h = getenv("KMERHIP_CAPACITY_HINT")) kc.capacity_hint(strtoull(h, nullptr, 10));
         if (!save.empty()) {  // src/main.rs:155-212: the index holds ALL k-mers, stdout honours --min-count
-            const PackedCounts all = kc.count_packed(path, false);
-            try {
-                save_index(all, save);
-            } catch (const Error &e) {
-                fprintf(stderr, "Failed to save index:\n %s\n", e.what());
-                return 1;
-            }
-            if (!quiet) fprintf(stderr, "saved: %s (%zu k-mers)\n", save.c_str(), all.keys.size());
-            write_counts(stdout, all, fmt, min_count);
+            bool saved = false;  // (one count: the pairs for the index, then stdout -- device text where the format has it)
+            kc.count_keep_and_write(path, stdout, [&](const PackedCounts &all) {
+                try {
+                    save_index(all, save);
+                } catch (const Error &e) {
+                    fprintf(stderr, "Failed to save index:\n %s\n", e.what());
+                    return false;
+                }
+                if (!quiet) fprintf(stderr, "saved: %s (%zu k-mers)\n", save.c_str(), all.keys.size());
+                return saved = true;
+            });
+            if (!saved) return 1;
         } else {
             kc.run(path);
         }

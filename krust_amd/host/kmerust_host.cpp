@@ -18,6 +18,11 @@
 #include <mutex>
 #include <thread>
 
+// The device-side writer is optional at link time: a library (or the sanitizer build's stub) without these entry points
+// leaves them null, and the host writer (write_counts) takes over.
+#pragma weak kh_result_text_begin
+#pragma weak kh_result_text_next
+
 namespace kmerust {
 
 // =============================================================================================
@@ -805,6 +810,95 @@ struct Session {
         pc.counts.resize(off);
         return pc;
     }
+    // ---- the output as text formatted on the device (kh_result_text_*) ----
+    // fasta / tsv: the shards' streams one after the other (their key sets are disjoint).  json: one rank only -- a document
+    // per shard is not a document -- the host writer takes the multi-rank case.  KMERUST_HOST_FORMAT=1: always the host writer.
+    bool device_text_ok(OutputFormat fmt) const {
+        if (!kh_result_text_begin || !kh_result_text_next) return false;  // (a library without the entry points: make asan's stub)
+        const char *e = getenv("KMERUST_HOST_FORMAT");
+        if (e && e[0] && e[0] != '0') return false;
+        return fmt == OutputFormat::Fasta || fmt == OutputFormat::Tsv || (fmt == OutputFormat::Json && ctxs.size() == 1);
+    }
+    void write_text(FILE *out, OutputFormat fmt, uint64_t min_count) {
+        const uint32_t f = fmt == OutputFormat::Fasta ? KH_OUT_FASTA : fmt == OutputFormat::Tsv ? KH_OUT_TSV : KH_OUT_JSON;
+        timing().device_writer = true;
+        for (kh_ctx *c : ctxs) {
+            uint64_t nbytes = 0;
+            {
+                Lap lap(timing().result_s);
+                check_on(c, kh_result_text_begin(c, f, min_count, nullptr, &nbytes), "kh_result_text_begin");
+            }
+            Lap lap(timing().write_s);
+            stream_pieces(c, nbytes, out);
+        }
+        if (fflush(out) != 0 || ferror(out))  // (a full disk must not end as a shorter text and exit status 0)
+            throw Error(std::string("failed to write the output: ") + std::strerror(errno));
+    }
+    // Pieces of up to 64 MiB into a few pinned buffers: a second thread fwrite()s piece i while piece i + 1 travels (and the
+    // device formats piece i + 2).  A small text takes one pageable buffer: pinning would cost more than the copy.
+    static void stream_pieces(kh_ctx *c, uint64_t nbytes, FILE *out) {
+        if (nbytes <= (1u << 20)) {
+            std::vector<uint8_t> buf((size_t)std::max<uint64_t>(nbytes, 128));
+            for (;;) {
+                uint64_t n = 0;
+                check_on(c, kh_result_text_next(c, buf.data(), buf.size(), &n), "kh_result_text_next");
+                if (!n || fwrite(buf.data(), 1, (size_t)n, out) != (size_t)n) return;  // (a short write: write_text reports it)
+            }
+        }
+        const uint64_t piece = std::min<uint64_t>(64ull << 20, (nbytes + 4095) & ~4095ull);
+        const int nbuf = nbytes <= piece ? 1 : 3;
+        std::vector<void *> bufs;
+        std::mutex mu;
+        std::condition_variable cv;
+        std::deque<std::pair<int, uint64_t>> filled;
+        int free_bufs = nbuf;
+        bool done = false, write_failed = false;  // write_failed: the output no longer takes text -- nothing more is pulled
+        std::thread writer([&] {
+            for (;;) {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return done || !filled.empty(); });
+                if (filled.empty()) return;
+                const auto job = filled.front();
+                filled.pop_front();
+                lk.unlock();
+                const bool ok = write_failed || fwrite(bufs[job.first], 1, (size_t)job.second, out) == (size_t)job.second;
+                lk.lock();
+                if (!ok) write_failed = true;
+                ++free_bufs;
+                cv.notify_all();
+            }
+        });
+        int rc = KH_OK;
+        const char *what = "kh_host_alloc";
+        for (int i = 0; i < nbuf && rc == KH_OK; ++i) {
+            void *p = nullptr;
+            rc = kh_host_alloc(&p, piece);
+            if (rc == KH_OK) bufs.push_back(p);
+        }
+        for (int i = 0; rc == KH_OK; i = (i + 1) % nbuf) {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return free_bufs > 0; });  // (the writer takes the buffers in the order they were filled)
+                if (write_failed) break;
+                --free_bufs;
+            }
+            uint64_t n = 0;
+            what = "kh_result_text_next";
+            rc = kh_result_text_next(c, (uint8_t *)bufs[i], piece, &n);
+            if (rc != KH_OK || n == 0) break;
+            std::lock_guard<std::mutex> lk(mu);
+            filled.push_back({i, n});
+            cv.notify_all();
+        }
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            done = true;
+            cv.notify_all();
+        }
+        writer.join();
+        for (void *p : bufs) kh_host_free(p);
+        check_on(c, rc, what);
+    }
     std::vector<std::pair<uint64_t, uint64_t>> histogram(uint64_t min_count) {
         Lap lap(timing().result_s);
         std::map<uint64_t, uint64_t> sum;  // a histogram of disjoint shards is element-wise additive
@@ -880,7 +974,32 @@ void KmerCounter::count_to_writer(const std::string &path, FILE *out) const {
         write_histogram(out, histogram(path));
         return;
     }
-    write_counts(out, count_packed(path, true), format_, 1);
+    const SequenceFormat f = resolve_format(input_format_, is_stdin_path(path) ? nullptr : &path);
+    const bool q = wants_quality(*this, f, min_quality_, path);
+    Session s(*this, q, plain_file_bytes(path));
+    s.count_file(path, f, q);
+    if (s.device_text_ok(format_)) {  // the text comes from the device: no pairs cross the link, no formatting loop here
+        s.write_text(out, format_, min_count_);
+        return;
+    }
+    const PackedCounts pc = s.result(min_count_);
+    Lap lap(timing().write_s);
+    write_counts(out, pc, format_, 1);
+}
+
+void KmerCounter::count_keep_and_write(const std::string &path, FILE *out, const std::function<bool(const PackedCounts &)> &keep) const {
+    const SequenceFormat f = resolve_format(input_format_, is_stdin_path(path) ? nullptr : &path);
+    const bool q = wants_quality(*this, f, min_quality_, path);
+    Session s(*this, q, plain_file_bytes(path));
+    s.count_file(path, f, q);
+    const PackedCounts all = s.result(1);  // (the index stores pairs: kh_result_copy)
+    if (!keep(all)) return;
+    if (format_ == OutputFormat::Histogram || !s.device_text_ok(format_)) {
+        Lap lap(timing().write_s);
+        write_counts(out, all, format_, min_count_);
+    } else {
+        s.write_text(out, format_, min_count_);
+    }
 }
 
 void KmerCounter::run(const std::string &path) const { count_to_writer(path, stdout); }

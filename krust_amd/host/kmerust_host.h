@@ -89,6 +89,9 @@ public:
     void run(const std::string &path) const;
     // count_to_writer() (builder.rs:403-460)
     void count_to_writer(const std::string &path, FILE *out) const;
+    // `kmerust --save`: ONE count; all pairs (for the index) go to `keep`, and when it returns true the records with
+    // count >= min_count are written to `out` in the configured format (src/main.rs:155-212)
+    void count_keep_and_write(const std::string &path, FILE *out, const std::function<bool(const PackedCounts &)> &keep) const;
 
     size_t get_k() const { return k_; }
 
@@ -119,6 +122,7 @@ struct Timing {
     double destroy_s = 0;  // releasing the device context(s)
     uint64_t bytes_read = 0, chunks = 0;
     bool text_path = false;  // records were found on the device (kh_push_text)
+    bool device_writer = false;  // the output text was formatted on the device (kh_result_text_*), not by write_counts
 };
 Timing &timing();
 bool &leak_at_exit();  // the CLI sets it: device contexts are not torn down before the process ends

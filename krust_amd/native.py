@@ -25,6 +25,7 @@ KH_ERR_FORMAT = -9
 KH_ERR_RCCL = -10
 KH_ERR_PEER = -11
 TEXT_FASTA, TEXT_FASTQ = 1, 2
+KH_OUT_FASTA, KH_OUT_TSV, KH_OUT_JSON = 1, 2, 3  # kh_result_text_begin
 
 
 class KhConfig(C.Structure):
@@ -75,6 +76,9 @@ SYMBOLS = {
     "kh_result_size": (C.c_int, [_P, _U64, C.POINTER(_U64)]),
     "kh_result_copy": (C.c_int, [_P, _P, _P, _U64, _U64, C.POINTER(_U64)]),
     "kh_result_copy_device": (C.c_int, [_P, _P, _P, _U64, _U64, C.POINTER(_U64)]),
+    "kh_result_text_begin": (C.c_int, [_P, C.c_uint32, _U64, C.POINTER(_U64), C.POINTER(_U64)]),
+    "kh_result_text_next": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
+    "kh_result_text_next_device": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
     "kh_histogram": (C.c_int, [_P, _U64, _P, _P, _U64, C.POINTER(_U64)]),
     "kh_lookup": (C.c_int, [_P, _P, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
@@ -173,6 +177,11 @@ def _addr(a):
 
 def _text_format(fmt):
     return {"fasta": TEXT_FASTA, "fastq": TEXT_FASTQ, TEXT_FASTA: TEXT_FASTA, TEXT_FASTQ: TEXT_FASTQ}[fmt]
+
+
+def _out_format(fmt):
+    return {"fasta": KH_OUT_FASTA, "tsv": KH_OUT_TSV, "json": KH_OUT_JSON,
+            KH_OUT_FASTA: KH_OUT_FASTA, KH_OUT_TSV: KH_OUT_TSV, KH_OUT_JSON: KH_OUT_JSON}[fmt]
 
 
 class DeviceCounter:
@@ -298,6 +307,51 @@ class DeviceCounter:
     def as_str_dict(self, min_count=1):
         """HashMap<String,u64> of into_hashmap (src/run.rs:573-582)."""
         return {unpack(key, self.k): c for key, c in self.as_dict(min_count).items()}
+
+    # -- output as text, formatted on the device -----------------------------
+    def result_text_begin(self, format, min_count=1):
+        """Starts (or restarts) the text stream of the records with count >= min_count; format: "fasta" | "tsv" | "json".
+        Returns (n_records, n_bytes) of the whole stream."""
+        nr, nb = _U64(0), _U64(0)
+        self._check(lib().kh_result_text_begin(self._h, _out_format(format), int(min_count), C.byref(nr), C.byref(nb)))
+        return int(nr.value), int(nb.value)
+
+    def result_text_next(self, buf, cap=None):
+        """The next piece (whole records, at most cap bytes) into `buf`: a writable numpy uint8 array (pageable, or a
+        PinnedArray's) or an integer host address with `cap`.  Returns the bytes written; 0 = the stream has ended.
+        Raises KmerHipError with status KH_ERR_RANGE when cap is smaller than the next record (nothing is consumed)."""
+        if isinstance(buf, np.ndarray):
+            assert buf.dtype == np.uint8 and buf.flags.c_contiguous and buf.flags.writeable
+            addr, cap = buf.ctypes.data, buf.size if cap is None else min(int(cap), buf.size)
+        else:
+            addr, cap = int(buf), int(cap)
+        n = _U64(0)
+        self._check(lib().kh_result_text_next(self._h, addr, cap, C.byref(n)))
+        return int(n.value)
+
+    def result_text(self, format, min_count=1, piece_bytes=8 << 20):
+        """Generator over the table as text: `bytes` pieces of at most piece_bytes that end at record ends and whose
+        concatenation is the whole document (the reference's output_counts, src/run.rs:441-486, formatted on the device)."""
+        self.result_text_begin(format, min_count)
+        buf = np.empty(max(int(piece_bytes), 1), dtype=np.uint8)
+        while True:
+            n = self.result_text_next(buf)
+            if n == 0:
+                return
+            yield buf[:n].tobytes()
+
+    def result_text_device(self, out, cap=None, format=None, min_count=1):
+        """The next piece into DEVICE memory: `out` is a uint8 tensor on this context's device, or an integer device address
+        with `cap`.  format given: the stream is (re)started first.  Returns the bytes written; 0 = the stream has ended."""
+        if format is not None:
+            self.result_text_begin(format, min_count)
+        if isinstance(out, int):
+            addr, cap = out, int(cap)
+        else:
+            addr, cap = out.data_ptr(), out.numel() * out.element_size() if cap is None else int(cap)
+        n = _U64(0)
+        self._check(lib().kh_result_text_next_device(self._h, addr, cap, C.byref(n)))
+        return int(n.value)
 
     def histogram(self, min_count=1):
         cap = 1 << 12
