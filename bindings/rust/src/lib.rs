@@ -98,6 +98,10 @@ pub mod sys {
         pub fn kh_histogram(ctx: *mut KhCtx, min_count: u64, count: *mut u64, freq: *mut u64,
                             cap: u64, n: *mut u64) -> c_int;
         pub fn kh_lookup(ctx: *mut KhCtx, keys: *const u64, n: u64, counts: *mut u64) -> c_int;
+        /// per-base abundance: out[i] = the table's count of the k-mer that starts at byte i (saturated at 0xFFFF_FFFE),
+        /// 0xFFFF_FFFF (KH_PROFILE_NO_WINDOW) where counting would see no window; reads the table only
+        pub fn kh_profile_device(ctx: *mut KhCtx, d_bases: *const u8, d_qual: *const u8, n: u64, d_out: *mut u32) -> c_int;
+        pub fn kh_profile(ctx: *mut KhCtx, bases: *const u8, qual: *const u8, n: u64, out: *mut u32) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
         pub fn kh_result_text_begin(ctx: *mut KhCtx, format: u32, min_count: u64, n_records: *mut u64,
                                     n_bytes: *mut u64) -> c_int;
@@ -138,6 +142,8 @@ pub enum HipError {
 
 /// `KMERHIP_ABI_VERSION` of the `include/kmerhip.h` that `mod sys` mirrors: the structs above are laid out for it.
 pub const ABI_VERSION: c_int = 2;
+/// `KH_PROFILE_NO_WINDOW`: an entry of [`HipKmerMap::profile`] where counting would see no window
+pub const PROFILE_NO_WINDOW: u32 = 0xFFFF_FFFF;
 
 /// The record formats of `kh_result_text_begin` (`KH_OUT_*`): the reference's `OutputFormat` without the histogram.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -321,6 +327,21 @@ impl HipKmerMap {
         }
         check(self.ctx, rc)?;
         Ok(true)
+    }
+
+    /// The table's count of the canonical k-mer at every window start of `bases` -- a flat buffer as `push` takes it, records
+    /// separated by a byte outside `ACGTacgt`, `qual` masking as in counting -- one `u32` per byte: the count (saturated at
+    /// `0xFFFF_FFFE`, 0 = absent) or [`PROFILE_NO_WINDOW`] where there is no window (N, soft mask, low quality, the last
+    /// k-1 bytes).  Reads the table only (`kh_profile`); pushes still pending are counted first.
+    pub fn profile(&mut self, bases: &[u8], qual: Option<&[u8]>) -> Result<Vec<u32>, HipError> {
+        if let Some(q) = qual {
+            assert_eq!(q.len(), bases.len(), "qual must be as long as bases");
+        }
+        let mut out = vec![0u32; bases.len()];
+        check(self.ctx, unsafe {
+            sys::kh_profile(self.ctx, bases.as_ptr(), qual.map_or(std::ptr::null(), |q| q.as_ptr()), bases.len() as u64, out.as_mut_ptr())
+        })?;
+        Ok(out)
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

@@ -229,6 +229,26 @@ int kh_histogram(kh_ctx *ctx, uint64_t min_count, uint64_t *count, uint64_t *fre
 /* counts[i] = count of packed canonical key keys[i], 0 if absent
  * (`kmerust query`, src/main.rs:264-280). */
 int kh_lookup(kh_ctx *ctx, const uint64_t *keys, uint64_t n, uint64_t *counts);
+/* Per-base abundance of new sequences against the table: out[i] = the table's count of the canonical k-mer of bytes
+ * i .. i+k-1, for every i < n (what `jellyfish query -s` / `kmc_tools filter` ask of a k-mer database, per read).
+ * INPUT as kh_push / kh_push_device: a flat buffer, records separated by >= 1 byte outside ACGTacgt, an optional parallel
+ * quality buffer that masks iff it is given AND the context has a min_quality (0xFF is the filler that never masks).
+ * OUTPUT: n entries, indexed by the window START, every one of them written:
+ *   - the count, saturated at 0xFFFFFFFE;  0 = a valid window whose k-mer the table does not hold
+ *   - KH_PROFILE_NO_WINDOW where counting would see no window at i: a byte outside ACGTacgt or a quality byte below the
+ *     threshold among the k, or i > n - k (the last k-1 entries; all of them when n < k)
+ * n == 0 is KH_OK.  Both calls only READ, like kh_lookup: pushes still pending are counted first, the table is read in the
+ * form it is in (kh_stats.slot_bytes stays what it was), no count changes, a kh_result_text_* stream in progress goes on,
+ * and a bad argument (NULL with n > 0, an out that is not 4-byte aligned: KH_ERR_BAD_ARG) leaves the context usable.
+ * SHARDS (kh_set_shard, or after kh_merge_across): a valid window whose k-mer ANOTHER shard owns reads 0 here, so the
+ * element-wise sum over the ranks' profiles of the same sequences -- at the positions that are not KH_PROFILE_NO_WINDOW,
+ * which are the same on every rank -- is the profile against the full table.
+ * kh_profile_device: buffers in this device's memory (d_bases / d_qual at any alignment); returns when d_out is complete.
+ * kh_profile: host memory, pageable or -- no bounce -- of kh_host_alloc / kh_host_register; streamed in chunks through
+ * pinned staging of the context (released by kh_destroy), transfers of one chunk beside the kernel of the next. */
+#define KH_PROFILE_NO_WINDOW 0xFFFFFFFFu
+int kh_profile_device(kh_ctx *ctx, const uint8_t *d_bases, const uint8_t *d_qual, uint64_t n, uint32_t *d_out);
+int kh_profile(kh_ctx *ctx, const uint8_t *bases, const uint8_t *qual, uint64_t n, uint32_t *out);
 
 /* ---- multi-GPU merge (no reference counterpart) ----------- */
 /* Owner shard of a packed canonical k-mer among nparts shards: a fast-range of the top bits of

@@ -6,6 +6,7 @@
 //   input.hip     kh_push* / kh_push_text*: staging, device accumulation, record scanning
 //   merge.hip     exports and merges of one context (pairs, dense, region-ordered)
 //   format.hip    kh_result_text_*: the table formatted as text on the device and streamed out in pieces
+//   profile.hip   kh_profile*: the table's count at every window start of new sequences
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
 //
@@ -107,6 +108,7 @@ struct Knobs {
     bool heads_always = false;       // KMERHIP_HEADS_ALWAYS=1: every fresh pass leaves the exchange-head counts behind, communicator or not
     u64 table_room_mb = 0;           // KMERHIP_TABLE_ROOM_MB: what the sample-sized table may take, as if the device had no more
     bool stop_after_p1 = false, stop_after_p2 = false;  // ablation builds (KH_ABL*)
+    u64 profile_chunk_kb = 0;        // KMERHIP_PROFILE_CHUNK_KB: window starts per chunk of kh_profile, in units of 1024 (0: sized from the call)
 };
 inline const char *env_of(const char *name) {
     const char *e = getenv(name);
@@ -309,6 +311,14 @@ struct kh_ctx {
     u64 *ts_roff = nullptr;       u64 ts_roff_cap = 0;   // exclusive scans of the two
     u64 *ts_boff = nullptr;       u64 ts_boff_cap = 0;
 
+    // ---- kh_profile: the chunks of the host form (profile.hip) ----
+    // two device buffers [bases | qualities | profile] for pf_chunk window starts each, their pinned twins (the bounce of pageable
+    // caller memory), and per buffer the events "input is on the device", "kernel done", "profile is in host memory"
+    uint8_t *pf_d[2] = {nullptr, nullptr};
+    uint8_t *pf_h[2] = {nullptr, nullptr};
+    u64 pf_chunk = 0;
+    hipEvent_t pf_in[2] = {nullptr, nullptr}, pf_run[2] = {nullptr, nullptr}, pf_out[2] = {nullptr, nullptr};
+
     bool poisoned = false;
     std::string last_error;
 };
@@ -378,6 +388,7 @@ int flush_acc(kh_ctx *c, bool carry);
 int flush_text(kh_ctx *c);
 int scan_unscanned(kh_ctx *c);
 bool is_pinned_host(const void *p);
+void staged_memcpy(void *dst, const void *src, size_t n);  // several threads for a large copy
 // ready: the event behind which d_src is complete (nullptr: it was produced on the compute stream, which is then drained)
 int d2h_staged(kh_ctx *c, void *dst, const void *d_src, u64 bytes, hipEvent_t ready = nullptr);
 // ---- merge.hip
@@ -396,6 +407,8 @@ int merge_regions(kh_ctx *c, int fmt, uint32_t nsenders, uint64_t sender_regions
 void comm_release(kh_ctx *c);
 // ---- format.hip
 void text_release(kh_ctx *c);  // kh_destroy: the text stream's buffers and events
+// ---- profile.hip
+void profile_release(kh_ctx *c);  // kh_destroy: the chunk buffers and events of kh_profile
 
 // ---- stage timing: HIP events on the launch stream, resolved lazily ---------------------------
 struct StageTimer {

@@ -39,6 +39,7 @@ void read_knobs(Knobs &k) {
     k.heads_always = env_of("KMERHIP_HEADS_ALWAYS") != nullptr;
     k.stop_after_p1 = env_of("KMERHIP_STOP_AFTER_P1") != nullptr;
     k.stop_after_p2 = env_of("KMERHIP_STOP_AFTER_P2") != nullptr;
+    if (const char *e = env_of("KMERHIP_PROFILE_CHUNK_KB")) k.profile_chunk_kb = strtoull(e, nullptr, 10);
 #endif
 }
 
@@ -534,6 +535,8 @@ extern "C" void kh_destroy(kh_ctx *c) {
     drain_events(c);
     if (c->cstream) (void)hipStreamSynchronize(c->cstream);
     text_release(c);
+    if (c->cstream2) (void)hipStreamSynchronize(c->cstream2);
+    profile_release(c);
     for (int i = 0; i < 2; ++i) {
         if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
         if (c->acc[i]) (void)hipFree(c->acc[i]);

@@ -1,0 +1,322 @@
+// profile.hip -- kh_profile / kh_profile_device: the table's count of the canonical k-mer at every window start of new
+// sequences (what `jellyfish query -s` answers per read).  No reference counterpart beyond `kmerust query` for ONE k-mer
+// (src/main.rs:264-280); the window rules are those of counting (src/run.rs:526-571), by construction: the kernel is built
+// from the counting path's tile staging and Roller (kernels.hip.h) and differs from count_direct_kernel only in what it does
+// with a key -- a read of its slot where that kernel issues an atomic.
+//   profile_kernel<QUAL, TAB>      TAB = PfWide: the 16-byte table; PfNarrow: the 8-byte image (partition.hip.h), as it is
+//   kh_profile_device              one launch over the caller's device buffers
+//   kh_profile                     the same in chunks through pinned staging: H2D, kernel and D2H of successive chunks overlap
+#include "ctx.hip.h"
+
+namespace kh {
+
+constexpr uint32_t PF_NO_WINDOW = KH_PROFILE_NO_WINDOW;
+constexpr uint32_t PF_SAT = 0xFFFFFFFEu;  // the largest count an entry can say
+// a tile's 4096 results in LDS, one pad word per 32: lane l writes word j of its 16 to bank (j + l / 2 + 16 (l & 1)) mod 32 and
+// the store phase reads words 4 apart -- both without a bank conflict
+constexpr int PF_LDS = TILE + TILE / 32;
+__device__ __forceinline__ int pf_lds(int e) { return e + (e >> 5); }
+
+__device__ __forceinline__ uint32_t pf_sat(u64 count) { return count > PF_SAT ? PF_SAT : (uint32_t)count; }
+
+// The two table forms behind one interface: ref() = where a key's probe sequence starts (and whether this -- possibly shard --
+// table can hold the key at all), load() = its first slot, resolve() = the count, probing on from that slot.  free_word() is
+// what a free slot reads as: resolve() answers 0 to it, so a window that loads nothing (a key of another shard) needs no branch.
+struct PfWide {
+    TableGeom tg;
+    typedef uint4 Word;
+    struct Ref {
+        const Slot *reg;
+        u64 key;
+        uint32_t off;
+        bool mine;
+    };
+    __device__ __forceinline__ Ref ref(u64 key) const {
+        const u64 H0 = kh_table_hash(key, tg.k);
+        Ref r;
+        // (a shard holds only keys of its hash range, and places them by the bits below the owner's: the rule of ntable_lookup_kernel)
+        r.mine = !tg.shard_shift || (H0 >> (64 - tg.shard_shift)) == tg.shard_index;
+        const u64 H = H0 << tg.shard_shift;
+        r.reg = tg.table + region_of(tg, H) * REGION_SLOTS;
+        r.off = start_of(tg, H);
+        r.key = key;
+        return r;
+    }
+    __device__ static __forceinline__ Word free_word() { return make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u); }
+    __device__ static __forceinline__ Word load(const Ref &r) { return *reinterpret_cast<const uint4 *>(&r.reg[r.off]); }
+    __device__ static __forceinline__ uint32_t resolve(const Ref &r, Word w) {
+        uint32_t off = r.off;
+        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
+            const u64 sk = ((u64)w.y << 32) | w.x;
+            if (sk == r.key) return pf_sat(((u64)w.w << 32) | w.z);
+            if (sk == KH_EMPTY_KEY) return 0u;
+            off = (off + 1) & REGION_MASK;
+            w = *reinterpret_cast<const uint4 *>(&r.reg[off]);
+        }
+        return 0u;
+    }
+};
+
+struct PfNarrow {
+    const u64 *ntab;
+    PartGeom g;
+    typedef u64 Word;
+    struct Ref {
+        const u64 *reg;
+        uint32_t pay;
+        uint32_t off;
+        bool mine;
+    };
+    __device__ __forceinline__ Ref ref(u64 key) const {
+        const u64 H0 = kh_table_hash(key, g.k);
+        Ref r;
+        r.mine = !g.shard_shift || (H0 >> (64 - g.shard_shift)) == g.shard_index;
+        const u64 H = H0 << g.shard_shift;
+        r.pay = Pay<uint32_t>::make(key, H, g);
+        r.reg = ntab + ((u64)kh_p1_of(H, g.p1_bits) * g.b2 + kh_bucket_of_x(r.pay, g.b2)) * REGION_SLOTS;
+        r.off = narrow_start(g, r.pay);
+        return r;
+    }
+    __device__ static __forceinline__ Word free_word() { return 0ull; }
+    __device__ static __forceinline__ Word load(const Ref &r) { return r.reg[r.off]; }
+    __device__ static __forceinline__ uint32_t resolve(const Ref &r, Word w) {
+        uint32_t off = r.off;
+        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
+            if ((w >> 32) == 0) return 0u;
+            if ((uint32_t)w == r.pay) return pf_sat(w >> 32);
+            off = (off + 1) & REGION_MASK;
+            w = r.reg[off];
+        }
+        return 0u;
+    }
+};
+
+// out[i] for every window start i < nout of the data [vbeg, vend) (virtual positions over abase, as in count_direct_kernel):
+// the count of the window's canonical k-mer, or PF_NO_WINDOW where counting would see no window.  A lane's 16 results are the
+// windows ENDING at its 16 bases -- entries p0 - (k - 1) - vbeg .. + 15 of out -- so a tile's 4096 results are one contiguous
+// run of out, k - 1 entries behind the tile: they go through LDS and leave as whole 16-byte units at 16-byte-aligned
+// addresses (a wave's store instruction is then 1 KiB of consecutive lines), with single words only in front of the first
+// aligned unit, behind the last, and at the two ends of out.  Tiles abut in out as they do in the data: every entry is
+// written exactly once.  The tiles run k - 1 positions past the data, where every window is invalid: the trailing entries.
+template <bool QUAL, typename TAB>
+__global__ __launch_bounds__(BLOCK) void profile_kernel(const uint8_t *__restrict__ abase, const uint8_t *__restrict__ qbase,
+                                                        int qaligned, u64 vbeg, u64 vend, u64 ntiles, uint32_t tiles_per_block,
+                                                        uint32_t k, uint32_t thr, TAB tab, uint32_t *__restrict__ out, u64 nout) {
+    __shared__ uint32_t s_code[2][BLOCK + 2];
+    __shared__ uint16_t s_val[2][BLOCK + 2];
+    __shared__ uint32_t s_out[PF_LDS];
+
+    const int tid = threadIdx.x;
+    const u64 tb = (u64)blockIdx.x * tiles_per_block;
+    u64 te = tb + tiles_per_block;
+    if (te > ntiles) te = ntiles;
+
+    int buf = 0;
+    for (u64 t = tb; t < te; ++t, buf ^= 1) {
+        const WinCtx w = stage_tile<QUAL, BLOCK>(s_code, s_val, buf, t == tb, tid, abase, qbase, qaligned, t, vbeg, vend, thr);
+        Roller roll;
+        roll.init(w, k, 0);
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            u64 key[8];
+            typename TAB::Ref ref[8];
+            typename TAB::Word first[8];
+            uint32_t ok = 0;
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) ok |= (uint32_t)roll.next(half * 8 + jj, key[jj]) << jj;
+            // eight first-slot loads in flight before the first of them is looked at (one random table line per valid window)
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+                ref[jj] = tab.ref(key[jj]);
+                first[jj] = TAB::free_word();
+                if ((ok & (1u << jj)) && ref[jj].mine) first[jj] = TAB::load(ref[jj]);
+            }
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+                const uint32_t res = (ok & (1u << jj)) ? TAB::resolve(ref[jj], first[jj]) : PF_NO_WINDOW;
+                s_out[pf_lds(tid * CHUNK + half * 8 + jj)] = res;
+            }
+        }
+        __syncthreads();
+        // (the next tile's results are written behind the barrier of its stage_tile: every lane is past these reads by then)
+        const int64_t T0 = (int64_t)(t * (u64)TILE) - (int64_t)(k - 1) - (int64_t)vbeg;  // entry of out the tile's first result is
+        const uint32_t sh = (uint32_t)(-((int64_t)((uintptr_t)out >> 2) + T0)) & 3u;      // results in front of the first aligned unit
+        if ((uint32_t)tid < sh) {
+            const int64_t gi = T0 + tid;
+            if (gi >= 0 && (u64)gi < nout) out[gi] = s_out[tid];
+        }
+#pragma unroll
+        for (int r = 0; r < TILE / 4 / BLOCK; ++r) {
+            const int e0 = (int)sh + 4 * (tid + r * BLOCK);
+            const int64_t gi = T0 + e0;
+            if (e0 + 3 < TILE && gi >= 0 && (u64)gi + 3 < nout) {
+                *reinterpret_cast<uint4 *>(out + gi) =
+                    make_uint4(s_out[pf_lds(e0)], s_out[pf_lds(e0 + 1)], s_out[pf_lds(e0 + 2)], s_out[pf_lds(e0 + 3)]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int e = e0 + i;
+                    const int64_t g = gi + i;
+                    if (e < TILE && g >= 0 && (u64)g < nout) out[g] = s_out[pf_lds(e)];
+                }
+            }
+        }
+    }
+}
+
+}  // namespace kh
+
+namespace khi {
+
+constexpr u64 PF_CHUNK_MAX = 4ull << 20;   // window starts per chunk of kh_profile: 4 MiB of bases in, 16 MiB of profile out
+constexpr u64 PF_CHUNK_MIN = 64ull << 10;
+constexpr u64 PF_PAD = 64;                 // behind a chunk's bases: its k - 1 bytes of the next chunk, and the kernel's 16-byte loads
+
+void profile_release(kh_ctx *c) {
+    for (int i = 0; i < 2; ++i) {
+        if (c->pf_d[i]) (void)hipFree(c->pf_d[i]);
+        if (c->pf_h[i]) (void)hipHostFree(c->pf_h[i]);
+        c->pf_d[i] = c->pf_h[i] = nullptr;
+        hipEvent_t *ev[] = {&c->pf_in[i], &c->pf_run[i], &c->pf_out[i]};
+        for (hipEvent_t *e : ev) {
+            if (*e) (void)hipEventDestroy(*e);
+            *e = nullptr;
+        }
+    }
+    c->pf_chunk = 0;
+}
+
+namespace {
+
+u64 pf_in_stride(u64 chunk) { return (chunk + PF_PAD + 15) & ~15ull; }
+
+// Every window start i < nout of the n device-resident bytes -> d_out[i]; asynchronous on the compute stream.
+int profile_range(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 n, u64 nout, uint32_t *d_out) {
+    if (nout == 0) return KH_OK;
+    const u64 lead = (uintptr_t)d_bases & 15;
+    const uint8_t *abase = d_bases - lead;
+    const u64 vbeg = lead, vend = lead + n;
+    const bool use_qual = d_qual != nullptr && c->minq >= 0;
+    const uint8_t *qbase = use_qual ? d_qual - lead : nullptr;  // same virtual coordinates as the bases
+    const int qaligned = use_qual && (((uintptr_t)qbase) & 15) == 0;
+    uint32_t thr = 0;
+    if (use_qual) {
+        const int t = c->minq + 33;  // saturating_add(33) on u8, run.rs:538
+        thr = (uint32_t)(t > 255 ? 255 : t);
+    }
+    // the window that starts at entry i ends at position vbeg + i + k - 1
+    const u64 ntiles = (vbeg + (c->k - 1) + nout + kh::TILE - 1) / kh::TILE;
+    u64 blocks = ntiles < (u64)GRID_CAP ? ntiles : (u64)GRID_CAP;
+    const uint32_t tpb = (uint32_t)((ntiles + blocks - 1) / blocks);  // contiguous tiles per workgroup: the look-back is carried in LDS
+    blocks = (ntiles + tpb - 1) / tpb;
+    auto launch = [&](auto tab) {
+        typedef decltype(tab) TAB;
+        if (use_qual)
+            hipLaunchKernelGGL((kh::profile_kernel<true, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase, qbase, qaligned, vbeg,
+                               vend, ntiles, tpb, c->k, thr, tab, d_out, nout);
+        else
+            hipLaunchKernelGGL((kh::profile_kernel<false, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase,
+                               (const uint8_t *)nullptr, 0, vbeg, vend, ntiles, tpb, c->k, 0u, tab, d_out, nout);
+    };
+    if (c->narrow) launch(kh::PfNarrow{(const u64 *)c->ntab, c->narrow_g});
+    else launch(kh::PfWide{table_geom(c, c->table, c->cap)});
+    HIP_TRY(c, hipGetLastError());
+    return KH_OK;
+}
+
+// The two chunk buffers on the device ([bases | qualities | profile]) and their pinned twins, for `chunk` window starts each.
+int profile_buffers(kh_ctx *c, u64 chunk) {
+    if (!c->cstream) HIP_TRY(c, hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
+    if (!c->cstream2) HIP_TRY(c, hipStreamCreateWithFlags(&c->cstream2, hipStreamNonBlocking));
+    if (c->pf_chunk < chunk) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        profile_release(c);
+        const u64 bytes = 2 * pf_in_stride(chunk) + 4 * chunk;
+        for (int i = 0; i < 2; ++i) {
+            hipError_t e = hipMalloc((void **)&c->pf_d[i], bytes);
+            if (e == hipSuccess) e = hipHostMalloc((void **)&c->pf_h[i], bytes, hipHostMallocDefault);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                profile_release(c);
+                return fail(c, KH_ERR_OOM, "kh_profile: chunk buffers", e);
+            }
+        }
+        c->pf_chunk = chunk;
+    }
+    for (int i = 0; i < 2; ++i) {
+        hipEvent_t *ev[] = {&c->pf_in[i], &c->pf_run[i], &c->pf_out[i]};
+        for (hipEvent_t *e : ev)
+            if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    return KH_OK;
+}
+
+}  // namespace
+}  // namespace khi
+using namespace khi;
+
+extern "C" int kh_profile_device(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, uint64_t n, uint32_t *d_out) {
+    if (!c) return KH_ERR_BAD_ARG;
+    if (n && (!d_bases || !d_out)) return fail(c, KH_ERR_BAD_ARG, "kh_profile_device: NULL argument");
+    if ((uintptr_t)d_out & 3) return fail(c, KH_ERR_BAD_ARG, "kh_profile_device: d_out is not 4-byte aligned");
+    int rc = enter(c, true, true, false, true, true);
+    if (rc != KH_OK) return rc;
+    if (n == 0) return KH_OK;
+    rc = profile_range(c, d_bases, d_qual, n, n, d_out);
+    if (rc != KH_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (d_out is complete, and the caller's buffers may go)
+    return KH_OK;
+}
+
+extern "C" int kh_profile(kh_ctx *c, const uint8_t *bases, const uint8_t *qual, uint64_t n, uint32_t *out) {
+    if (!c) return KH_ERR_BAD_ARG;
+    if (n && (!bases || !out)) return fail(c, KH_ERR_BAD_ARG, "kh_profile: NULL argument");
+    if ((uintptr_t)out & 3) return fail(c, KH_ERR_BAD_ARG, "kh_profile: out is not 4-byte aligned");
+    int rc = enter(c, true, true, false, true, true);
+    if (rc != KH_OK) return rc;
+    if (n == 0) return KH_OK;
+    const bool with_qual = qual != nullptr && c->minq >= 0;
+    u64 chunk = PF_CHUNK_MIN;
+    while (chunk < n && chunk < PF_CHUNK_MAX) chunk *= 2;
+#if KH_TESTING
+    if (c->knobs.profile_chunk_kb) chunk = c->knobs.profile_chunk_kb << 10;  // (tests: chunk edges inside reads)
+#endif
+    if ((rc = profile_buffers(c, chunk)) != KH_OK) return rc;
+    // pinned / registered caller memory: the copy engine reads and writes it itself, no bounce through pf_h
+    const bool in_direct = is_pinned_host(bases) && (!with_qual || is_pinned_host(qual));
+    const bool out_direct = is_pinned_host(out);
+    const u64 stride = pf_in_stride(c->pf_chunk), k1 = c->k - 1;
+    const u64 nch = (n + chunk - 1) / chunk;
+    // Chunk j owns the window starts [j chunk, (j + 1) chunk) and is sent the bytes they need: its own and the k - 1 after them
+    // (the overlap).  A window is answered by the chunk that holds its start, so no entry of out is written twice.
+    auto starts = [&](u64 j) { return std::min(chunk, n - j * chunk); };
+    auto finish = [&](u64 j) -> int {  // chunk j has arrived in pinned memory: out of the bounce buffer
+        const int b = (int)(j & 1);
+        HIP_TRY(c, hipEventSynchronize(c->pf_out[b]));
+        if (!out_direct) staged_memcpy(out + j * chunk, c->pf_h[b] + 2 * stride, 4 * starts(j));
+        return KH_OK;
+    };
+    for (u64 j = 0; j < nch; ++j) {
+        // (the buffers of chunk j were those of chunk j - 2, which finish() saw complete in the last round)
+        const int b = (int)(j & 1);
+        const u64 a = j * chunk, ns = starts(j), len = std::min(ns + k1, n - a);
+        uint8_t *const d = c->pf_d[b], *const h = c->pf_h[b];
+        if (!in_direct) {
+            staged_memcpy(h, bases + a, len);
+            if (with_qual) staged_memcpy(h + stride, qual + a, len);
+        }
+        HIP_TRY(c, hipMemcpyAsync(d, in_direct ? bases + a : h, len, hipMemcpyHostToDevice, c->cstream));
+        if (with_qual) HIP_TRY(c, hipMemcpyAsync(d + stride, in_direct ? qual + a : h + stride, len, hipMemcpyHostToDevice, c->cstream));
+        HIP_TRY(c, hipEventRecord(c->pf_in[b], c->cstream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pf_in[b], 0));
+        uint32_t *const d_out = reinterpret_cast<uint32_t *>(d + 2 * stride);
+        if ((rc = profile_range(c, d, with_qual ? d + stride : nullptr, len, ns, d_out)) != KH_OK) return rc;
+        HIP_TRY(c, hipEventRecord(c->pf_run[b], c->stream));
+        // the profile of chunk j travels on a stream of its own, beside the kernel of chunk j + 1
+        HIP_TRY(c, hipStreamWaitEvent(c->cstream2, c->pf_run[b], 0));
+        HIP_TRY(c, hipMemcpyAsync(out_direct ? (void *)(out + a) : (void *)(h + 2 * stride), d_out, 4 * ns, hipMemcpyDeviceToHost, c->cstream2));
+        HIP_TRY(c, hipEventRecord(c->pf_out[b], c->cstream2));
+        if (j && (rc = finish(j - 1)) != KH_OK) return rc;
+    }
+    return finish(nch - 1);
+}

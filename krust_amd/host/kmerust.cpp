@@ -21,6 +21,7 @@ namespace kmerust {
 static const char *USAGE =
     "Usage: kmerust [OPTIONS] <K> [PATH]\n"
     "       kmerust query <INDEX> <KMER>\n"
+    "       kmerust query <INDEX> --sequences <PATH> [-i <INPUT_FORMAT>] [-Q <MIN_QUALITY>] [-f summary|profile] [-q]\n"
     "\n"
     "Arguments:\n"
     "  <K>     K-mer length (1-32)\n"
@@ -35,6 +36,11 @@ static const char *USAGE =
     "  -Q, --min-quality <MIN_QUALITY>    Minimum Phred quality score (0-93) for FASTQ bases\n"
     "      --gpus <N>                     Count on the first N GPUs of the node (RCCL merge of the per-GPU tables) [default: 1]\n"
     "      --devices <LIST>               The same with explicit HIP device ordinals, e.g. 0,2,5\n"
+    "\n"
+    "query --sequences: the index's count of the k-mer at every base of the sequences in <PATH>, one line per record.\n"
+    "  -f summary (default)  {record}\\t{windows}\\t{present}\\t{min}\\t{max}\\t{sum}\n"
+    "  -f profile            one count per window start, '-' where there is no k-mer (N, soft mask, low quality)\n"
+    "\n"
     "  -h, --help                         Print help\n"
     "  -V, --version                      Print version\n";
 
@@ -61,7 +67,97 @@ static uint64_t parse_u64(const std::string &s, const char *what, uint64_t max) 
     return v;
 }
 
+#if defined(__has_feature)
+#if __has_feature(address_sanitizer)
+#define KMERUST_UNDER_ASAN 1
+#endif
+#endif
+// kmerust query <INDEX> --sequences <PATH> [-i FMT] [-Q N] [-f summary|profile] [-q]: per-base abundance (no reference counterpart)
+static int run_query_sequences(int argc, char **argv) {
+    std::string index, path;
+    bool have_index = false, have_path = false, quiet = false;
+    SequenceFormat in_fmt = SequenceFormat::Auto;
+    ProfileFormat fmt = ProfileFormat::Summary;
+    const char *fmt_name = "summary";
+    int min_quality = -1;
+    size_t batch_bytes = 0;
+    auto value_of = [&](int &i, const std::string &arg, const char *name) -> std::string {
+        const size_t eq = arg.find('=');
+        if (arg.rfind("--", 0) == 0 && eq != std::string::npos) return arg.substr(eq + 1);
+        if (arg.rfind("--", 0) != 0 && arg.size() > 2) return arg.substr(2);  // -fVALUE
+        if (i + 1 >= argc) usage_error(std::string("a value is required for '") + name + "' but none was supplied");
+        return argv[++i];
+    };
+    for (int i = 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        const std::string key = a.rfind("--", 0) == 0 ? a.substr(0, a.find('=')) : a.substr(0, 2);
+        if (a == "-q" || a == "--quiet") {
+            quiet = true;
+        } else if (key == "--sequences") {
+            path = value_of(i, a, "--sequences <PATH>");
+            have_path = true;
+        } else if (key == "-f" || key == "--format") {
+            const std::string v = value_of(i, a, "--format <FORMAT>");
+            if (v == "summary") fmt = ProfileFormat::Summary, fmt_name = "summary";
+            else if (v == "profile") fmt = ProfileFormat::Profile, fmt_name = "profile";
+            else usage_error("invalid value '" + v + "' for '--format <FORMAT>'\n  [possible values: summary, profile]");
+        } else if (key == "-i" || key == "--input-format") {
+            const std::string v = value_of(i, a, "--input-format <INPUT_FORMAT>");
+            if (v == "auto") in_fmt = SequenceFormat::Auto;
+            else if (v == "fasta") in_fmt = SequenceFormat::Fasta;
+            else if (v == "fastq") in_fmt = SequenceFormat::Fastq;
+            else usage_error("invalid value '" + v + "' for '--input-format <INPUT_FORMAT>'\n  [possible values: auto, fasta, fastq]");
+        } else if (key == "-Q" || key == "--min-quality") {
+            min_quality = (int)parse_u64(value_of(i, a, "--min-quality <MIN_QUALITY>"), "--min-quality <MIN_QUALITY>", 255);
+        } else if (key == "--__batch-kb") {  // hidden test hook, as __parse: KiB of flat records per kh_profile call
+            batch_bytes = (size_t)parse_u64(value_of(i, a, "--__batch-kb <N>"), "--__batch-kb <N>", 1u << 22) << 10;
+        } else if (a.size() > 1 && a[0] == '-' && a != "-") {
+            usage_error("unexpected argument '" + a + "' found");
+        } else if (!have_index) {
+            index = a;
+            have_index = true;
+        } else {
+            usage_error("unexpected argument '" + a + "' found");
+        }
+    }
+    if (!have_index) usage_error("the following required arguments were not provided:\n  <INDEX>\n\nUsage: kmerust query <INDEX> --sequences <PATH>");
+    if (!have_path) usage_error("the following required arguments were not provided:\n  --sequences <PATH>\n\nUsage: kmerust query <INDEX> --sequences <PATH>");
+    const bool from_stdin = is_stdin_path(path);
+    if (!from_stdin) {
+        struct stat st;
+        if (stat(path.c_str(), &st) != 0) {
+            fprintf(stderr, "Problem with arguments:\n File not found: %s\n", path.c_str());
+            return 1;
+        }
+    }
+    const SequenceFormat resolved = resolve_format(in_fmt, from_stdin ? nullptr : &path);
+    if (!quiet) {  // (the counting command's banner, with the index where that has k)
+        fprintf(stderr, "index: %s\n", index.c_str());
+        fprintf(stderr, "data: %s\n", from_stdin ? "<stdin>" : path.c_str());
+        if (in_fmt == SequenceFormat::Auto) fprintf(stderr, "input-format: %s (auto-detected)\n", format_name(resolved));
+        else fprintf(stderr, "input-format: %s\n", format_name(in_fmt));
+        fprintf(stderr, "reader: kmerhip\n");
+        fprintf(stderr, "output-format: %s\n", fmt_name);
+        if (min_quality >= 0) fprintf(stderr, "min-quality: %d\n", min_quality);
+        fprintf(stderr, "\n");
+    }
+    if (min_quality >= 0 && resolved == SequenceFormat::Fasta) fprintf(stderr, "warning: --min-quality is ignored for FASTA input\n");
+    if (min_quality >= 0 && from_stdin) fprintf(stderr, "warning: --min-quality is not yet supported for stdin input\n");
+#if !defined(__SANITIZE_ADDRESS__) && !defined(KMERUST_UNDER_ASAN) && !defined(KMERUST_ALWAYS_CLEAN_EXIT)  // (as cli_main)
+    leak_at_exit() = !getenv("KMERUST_CLEAN_EXIT");
+#endif
+    try {
+        query_sequences(index, path, in_fmt, min_quality, fmt, stdout, batch_bytes);
+    } catch (const Error &e) {
+        fprintf(stderr, "Application error:\n %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 static int run_query(int argc, char **argv) {
+    for (int i = 2; i < argc; ++i)
+        if (!strncmp(argv[i], "--sequences", 11) && (argv[i][11] == 0 || argv[i][11] == '=')) return run_query_sequences(argc, argv);
     if (argc != 4) usage_error("the following required arguments were not provided: <INDEX> <KMER>");
     PackedCounts idx;
     try {

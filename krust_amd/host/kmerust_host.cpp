@@ -22,6 +22,9 @@
 // leaves them null, and the host writer (write_counts) takes over.
 #pragma weak kh_result_text_begin
 #pragma weak kh_result_text_next
+// ... and so are the entry points of `query --sequences`: without them the command refuses cleanly instead of failing to link.
+#pragma weak kh_profile
+#pragma weak kh_merge_pairs
 
 namespace kmerust {
 
@@ -1049,6 +1052,89 @@ struct OutBuf {
     }
 };
 }  // namespace
+
+// =============================================================================================
+// per-base abundance against an index
+// =============================================================================================
+uint64_t write_profile_lines(FILE *out, const uint8_t *bases, const uint32_t *profile, size_t n, uint32_t k, ProfileFormat fmt,
+                             uint64_t first_ordinal) {
+    uint64_t records = 0;
+    std::string line;
+    char num[24];
+    for (size_t s = 0; s < n;) {
+        const void *nl = memchr(bases + s, '\n', n - s);
+        const size_t e = nl ? (size_t)((const uint8_t *)nl - bases) : n;  // (an unterminated last run is a record too)
+        const size_t len = e - s, starts = len >= k ? len - k + 1 : 0;
+        line.clear();
+        if (fmt == ProfileFormat::Summary) {
+            uint64_t windows = 0, present = 0, sum = 0;
+            uint32_t lo = 0, hi = 0;
+            for (size_t i = 0; i < starts; ++i) {
+                const uint32_t v = profile[s + i];
+                if (v == KH_PROFILE_NO_WINDOW) continue;
+                lo = windows ? std::min(lo, v) : v;
+                hi = windows ? std::max(hi, v) : v;
+                ++windows;
+                present += v > 0;
+                sum += v;
+            }
+            char buf[160];
+            snprintf(buf, sizeof buf, "%llu\t%llu\t%llu\t%u\t%u\t%llu", (unsigned long long)(first_ordinal + records),
+                     (unsigned long long)windows, (unsigned long long)present, lo, hi, (unsigned long long)sum);
+            line = buf;
+        } else {
+            for (size_t i = 0; i < starts; ++i) {
+                if (i) line.push_back(' ');
+                const uint32_t v = profile[s + i];
+                if (v == KH_PROFILE_NO_WINDOW) {
+                    line.push_back('-');
+                } else {
+                    const int w = snprintf(num, sizeof num, "%u", v);
+                    line.append(num, (size_t)w);
+                }
+            }
+        }
+        line.push_back('\n');
+        fwrite(line.data(), 1, line.size(), out);
+        ++records;
+        s = e + 1;
+    }
+    return records;
+}
+
+void query_sequences(const std::string &index_path, const std::string &path, SequenceFormat fmt, int min_quality, ProfileFormat out_fmt,
+                     FILE *out, size_t batch_bytes) {
+    if (!kh_profile || !kh_merge_pairs)
+        throw Error("query --sequences needs a kmerhip library with kh_profile and kh_merge_pairs; the one this program was built against has neither");
+    const PackedCounts idx = load_index(index_path);
+    const SequenceFormat resolved = resolve_format(fmt, is_stdin_path(path) ? nullptr : &path);
+    const bool want_qual = min_quality >= 0 && resolved == SequenceFormat::Fastq && !is_stdin_path(path);  // as counting: wants_quality()
+    kh_config cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.struct_size = sizeof(cfg);
+    cfg.k = idx.k;
+    cfg.min_quality = want_qual ? min_quality : -1;
+    cfg.device = -1;
+    cfg.capacity_hint = idx.keys.size();
+    struct Ctx {
+        kh_ctx *c = nullptr;
+        ~Ctx() {
+            if (c && !leak_at_exit()) kh_destroy(c);
+        }
+    } ctx;
+    Session::check_on(nullptr, kh_create(&ctx.c, &cfg), "kh_create");
+    Session::check_on(ctx.c, kh_merge_pairs(ctx.c, idx.keys.data(), idx.counts.data(), idx.keys.size()), "kh_merge_pairs");
+    const size_t batch = batch_bytes ? batch_bytes : (size_t)16 << 20;  // bytes of flat records per kh_profile call
+    std::vector<uint32_t> prof;
+    uint64_t ordinal = 0;
+    read_sequences(path, fmt, want_qual, batch, [&](const Batch &b) {
+        prof.resize(b.bases.size());
+        Session::check_on(ctx.c, kh_profile(ctx.c, b.bases.data(), want_qual && !b.qual.empty() ? b.qual.data() : nullptr, b.bases.size(), prof.data()),
+                          "kh_profile");
+        ordinal += write_profile_lines(out, b.bases.data(), prof.data(), b.bases.size(), idx.k, out_fmt, ordinal);
+    });
+    if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+}
 
 void write_counts(FILE *out, const PackedCounts &pc, OutputFormat fmt, uint64_t min_count) {
     OutBuf w(out);

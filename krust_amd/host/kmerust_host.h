@@ -132,6 +132,23 @@ std::string unpack_to_string(uint64_t bits, uint32_t k);  // src/kmer.rs:451-456
 void write_counts(FILE *out, const PackedCounts &pc, OutputFormat fmt, uint64_t min_count);
 void write_histogram(FILE *out, const std::vector<std::pair<uint64_t, uint64_t>> &hist);
 
+// ---- per-base abundance against an index (`kmerust query <INDEX> --sequences <PATH>`; no reference counterpart) ----------------
+enum class ProfileFormat { Summary, Profile };
+// One line per record of a flat batch -- a record is a '\n'-terminated run of `bases`, as read_sequences delivers it -- from the
+// batch's profile (kh_profile: profile[i] = count of the window that starts at byte i, KH_PROFILE_NO_WINDOW where there is none):
+//   Summary   {ordinal}\t{windows}\t{present}\t{min}\t{max}\t{sum}   windows = entries that are a window, present = those > 0,
+//             min / max over the windows (0 when there is none), sum as u64
+//   Profile   one token per window start 0 .. len-k, separated by single blanks: the count, or '-' where there is no window
+//             (a record shorter than k: an empty line)
+// Records are numbered from first_ordinal; returns the number of records written.
+uint64_t write_profile_lines(FILE *out, const uint8_t *bases, const uint32_t *profile, size_t n, uint32_t k, ProfileFormat fmt,
+                             uint64_t first_ordinal);
+// load_index, the pairs into a device table (kh_merge_pairs), then kh_profile per batch of read_sequences and the lines above.
+// min_quality: -1 = none; used for FASTQ files only, as in counting.  batch_bytes: flat record bytes per kh_profile call (0 = 16 MiB).
+// Throws Error.
+void query_sequences(const std::string &index_path, const std::string &path, SequenceFormat fmt, int min_quality, ProfileFormat out_fmt,
+                     FILE *out, size_t batch_bytes = 0);
+
 // ---- KMIX index (src/index.rs) -----------------------------------------------------------------
 uint32_t crc32_ieee(const uint8_t *data, size_t n, uint32_t crc = 0);  // src/index.rs:404-431
 void save_index(const PackedCounts &pc, const std::string &path);      // gzip if path ends in .gz

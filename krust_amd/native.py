@@ -26,6 +26,7 @@ KH_ERR_RCCL = -10
 KH_ERR_PEER = -11
 TEXT_FASTA, TEXT_FASTQ = 1, 2
 KH_OUT_FASTA, KH_OUT_TSV, KH_OUT_JSON = 1, 2, 3  # kh_result_text_begin
+PROFILE_NO_WINDOW = 0xFFFFFFFF  # KH_PROFILE_NO_WINDOW: an entry of kh_profile* where counting would see no window
 
 
 class KhConfig(C.Structure):
@@ -81,6 +82,8 @@ SYMBOLS = {
     "kh_result_text_next_device": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
     "kh_histogram": (C.c_int, [_P, _U64, _P, _P, _U64, C.POINTER(_U64)]),
     "kh_lookup": (C.c_int, [_P, _P, _U64, _P]),
+    "kh_profile_device": (C.c_int, [_P, _P, _P, _U64, _P]),
+    "kh_profile": (C.c_int, [_P, _P, _P, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
     "kh_set_shard": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "kh_set_region_window": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -371,6 +374,28 @@ class DeviceCounter:
         out = np.zeros(keys.size, dtype=np.uint64)
         self._check(lib().kh_lookup(self._h, keys.ctypes.data, keys.size, out.ctypes.data))
         return out
+
+    def profile(self, bases, qual=None, out=None):
+        """Per-base abundance: a uint32 array with one entry per byte of the flat buffer `bases` (records separated by a byte
+        outside ACGTacgt; `qual` masks as in counting) -- entry i is the table's count of the canonical k-mer of bytes
+        i .. i+k-1, saturated at 0xFFFFFFFE, 0 when the table does not hold it, PROFILE_NO_WINDOW where counting would see no
+        window.  Host memory, pageable or a PinnedArray's; out = a uint32 array to fill (e.g. a PinnedArray's: no bounce)."""
+        bp, kb = _addr(bases)
+        n = kb.size if kb is not None else 0
+        qp, kq = _addr(qual)
+        if kq is not None and kq.size != n:
+            raise ValueError("qual must have the same length as bases")
+        if out is None:
+            out = np.empty(n, dtype=np.uint32)
+        assert out.dtype == np.uint32 and out.flags.c_contiguous and out.flags.writeable and out.size >= n
+        self._check(lib().kh_profile(self._h, bp, qp, n, out.ctypes.data))
+        return out[:n]
+
+    def profile_device(self, d_bases, d_qual, n, d_out):
+        """The same on device memory: integer addresses (e.g. tensor.data_ptr()) of n bases, n quality bytes or None, and n
+        uint32 entries to fill, or torch tensors on this context's device.  Returns when d_out is complete."""
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        self._check(lib().kh_profile_device(self._h, ptr(d_bases), ptr(d_qual), int(n), ptr(d_out)))
 
     # -- multi-GPU merge ---------------------------------------------------
     def comm_init(self, nranks, rank, unique_id):
