@@ -102,6 +102,12 @@ pub mod sys {
         /// 0xFFFF_FFFF (KH_PROFILE_NO_WINDOW) where counting would see no window; reads the table only
         pub fn kh_profile_device(ctx: *mut KhCtx, d_bases: *const u8, d_qual: *const u8, n: u64, d_out: *mut u32) -> c_int;
         pub fn kh_profile(ctx: *mut KhCtx, bases: *const u8, qual: *const u8, n: u64, out: *mut u32) -> c_int;
+        /// the profile reduced per record on the device: `rec_start` has `nrec + 1` ascending offsets, row `r` (8 `u32`) is the
+        /// reduction over the window starts `rec_start[r] .. rec_start[r+1]` (KH_REC_* of the header name the words)
+        pub fn kh_profile_records_device(ctx: *mut KhCtx, d_bases: *const u8, d_qual: *const u8, n: u64, d_rec_start: *const u64,
+                                         nrec: u64, lo: u32, hi: u32, d_rows: *mut u32) -> c_int;
+        pub fn kh_profile_records(ctx: *mut KhCtx, bases: *const u8, qual: *const u8, n: u64, rec_start: *const u64, nrec: u64,
+                                  lo: u32, hi: u32, rows: *mut u32) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
         pub fn kh_result_text_begin(ctx: *mut KhCtx, format: u32, min_count: u64, n_records: *mut u64,
                                     n_bytes: *mut u64) -> c_int;
@@ -144,6 +150,24 @@ pub enum HipError {
 pub const ABI_VERSION: c_int = 2;
 /// `KH_PROFILE_NO_WINDOW`: an entry of [`HipKmerMap::profile`] where counting would see no window
 pub const PROFILE_NO_WINDOW: u32 = 0xFFFF_FFFF;
+
+/// One row of [`HipKmerMap::profile_records`] (`KH_REC_*`): the reduction of a record's profile entries that are a window.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct RecordAbundance {
+    /// entries of the record that are a window
+    pub windows: u32,
+    /// windows whose count is > 0
+    pub present: u32,
+    /// windows with `lo <= count <= hi`
+    pub in_range: u32,
+    /// min / max over the windows (0 when there is none)
+    pub min: u32,
+    pub max: u32,
+    /// sum of the saturated counts
+    pub sum: u64,
+    /// offset from the record start of the first window whose count is `< lo`
+    pub first_low: Option<u32>,
+}
 
 /// The record formats of `kh_result_text_begin` (`KH_OUT_*`): the reference's `OutputFormat` without the histogram.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -342,6 +366,25 @@ impl HipKmerMap {
             sys::kh_profile(self.ctx, bases.as_ptr(), qual.map_or(std::ptr::null(), |q| q.as_ptr()), bases.len() as u64, out.as_mut_ptr())
         })?;
         Ok(out)
+    }
+
+    /// [`profile`](Self::profile) reduced per record on the device (`kh_profile_records`): `rec_start` holds `nrec + 1`
+    /// ascending offsets into `bases` (the last one `<= bases.len()`), record `r` owns the window starts
+    /// `rec_start[r] .. rec_start[r+1]`.  32 bytes per record come back instead of 4 per base.
+    pub fn profile_records(&mut self, bases: &[u8], qual: Option<&[u8]>, rec_start: &[u64], lo: u32, hi: u32) -> Result<Vec<RecordAbundance>, HipError> {
+        if let Some(q) = qual {
+            assert_eq!(q.len(), bases.len(), "qual must be as long as bases");
+        }
+        let nrec = rec_start.len().saturating_sub(1);
+        let mut rows = vec![0u32; nrec * 8];
+        check(self.ctx, unsafe {
+            sys::kh_profile_records(self.ctx, bases.as_ptr(), qual.map_or(std::ptr::null(), |q| q.as_ptr()), bases.len() as u64,
+                                    rec_start.as_ptr(), nrec as u64, lo, hi, rows.as_mut_ptr())
+        })?;
+        Ok(rows.chunks_exact(8).map(|w| RecordAbundance {
+            windows: w[0], present: w[1], in_range: w[2], min: w[3], max: w[4], sum: (w[5] as u64) | ((w[6] as u64) << 32),
+            first_low: if w[7] == 0xFFFF_FFFF { None } else { Some(w[7]) },
+        }).collect())
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

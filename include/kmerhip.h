@@ -249,6 +249,38 @@ int kh_lookup(kh_ctx *ctx, const uint64_t *keys, uint64_t n, uint64_t *counts);
 #define KH_PROFILE_NO_WINDOW 0xFFFFFFFFu
 int kh_profile_device(kh_ctx *ctx, const uint8_t *d_bases, const uint8_t *d_qual, uint64_t n, uint32_t *d_out);
 int kh_profile(kh_ctx *ctx, const uint8_t *bases, const uint8_t *qual, uint64_t n, uint32_t *out);
+/* The same profile reduced per record ON THE DEVICE: one row of KH_REC_WORDS uint32 words per record instead of one word per base
+ * (what `kmerust query --sequences -f summary` prints and `kmerust filter` decides by) -- 32 bytes per record cross the link.
+ * Let P[0..n) be what kh_profile* writes for the same bases, qual, n and context.  rec_start has nrec + 1 ASCENDING entries with
+ * rec_start[nrec] <= n; record r owns the window starts rec_start[r] <= i < rec_start[r+1], and row r (words r*8 .. r*8+7 of
+ * rows) is the reduction below over P[i] for those i, skipping KH_PROFILE_NO_WINDOW.  Every row is written; an empty record, or
+ * one without a window, gives {0,0,0,0,0,0,0,0xFFFFFFFF}.  Segments need not coincide with separators: a caller whose records
+ * are '\n'-separated passes the record start bytes and n (a window that would reach over a separator is no window anyway).
+ * The counts are kh_profile's saturated ones (<= 0xFFFFFFFE), their sum is exact in 64 bits; lo > hi gives in_range == 0,
+ * lo == 0 gives first_low == 0xFFFFFFFF.
+ * Otherwise the contract of kh_profile: read-only, pending pushes are counted first, kh_stats.slot_bytes stays, a kh_result_text_*
+ * stream goes on, both table forms and shard tables are read as they are.  SHARDS: a window whose k-mer another shard owns reads 0,
+ * so `windows` is equal on every rank and `present` and `sum` ADD UP over the ranks to the full table's; min, max, in_range and
+ * first_low do NOT combine over ranks (a foreign key's 0 takes part in them).
+ * nrec == 0 is KH_OK and writes nothing; n == 0 writes nrec empty rows.  KH_ERR_BAD_ARG, the context usable afterwards: NULL with
+ * n or nrec > 0, rows not 4-byte aligned (rec_start not 8-byte aligned), and in the host form rec_start not ascending,
+ * rec_start[nrec] > n, or a record of 2^32 or more window starts.  For kh_profile_records_device those three are the caller's
+ * contract: the offsets are not read back to check them (offsets that break it give unspecified rows, nothing else).
+ * kh_profile_records streams the bases in chunks like kh_profile (same staging, released by kh_destroy); the rows stay on the
+ * device for the whole call and come back once at the end, rec_start goes up once. */
+#define KH_REC_WORDS 8        /* uint32 words per record row */
+#define KH_REC_WINDOWS 0      /* entries of the record that are a window (not KH_PROFILE_NO_WINDOW) */
+#define KH_REC_PRESENT 1      /* windows whose count is > 0 */
+#define KH_REC_IN_RANGE 2     /* windows with lo <= count <= hi */
+#define KH_REC_MIN 3          /* min / max over the windows; 0 when there is none */
+#define KH_REC_MAX 4
+#define KH_REC_SUM_LO 5       /* sum of the (saturated) counts as u64: low, high word */
+#define KH_REC_SUM_HI 6
+#define KH_REC_FIRST_LOW 7    /* offset from the record start of the first window whose count is < lo; 0xFFFFFFFF: none */
+int kh_profile_records_device(kh_ctx *ctx, const uint8_t *d_bases, const uint8_t *d_qual, uint64_t n, const uint64_t *d_rec_start,
+                              uint64_t nrec, uint32_t lo, uint32_t hi, uint32_t *d_rows);
+int kh_profile_records(kh_ctx *ctx, const uint8_t *bases, const uint8_t *qual, uint64_t n, const uint64_t *rec_start,
+                       uint64_t nrec, uint32_t lo, uint32_t hi, uint32_t *rows);
 
 /* ---- multi-GPU merge (no reference counterpart) ----------- */
 /* Owner shard of a packed canonical k-mer among nparts shards: a fast-range of the top bits of

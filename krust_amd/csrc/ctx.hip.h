@@ -318,6 +318,9 @@ struct kh_ctx {
     uint8_t *pf_h[2] = {nullptr, nullptr};
     u64 pf_chunk = 0;
     hipEvent_t pf_in[2] = {nullptr, nullptr}, pf_run[2] = {nullptr, nullptr}, pf_out[2] = {nullptr, nullptr};
+    // kh_profile_records: the rows (KH_REC_WORDS words per record) and the record offsets, on the device for the whole call
+    uint32_t *pr_rows = nullptr;  u64 pr_rows_cap = 0;  // records
+    u64 *pr_rec = nullptr;        u64 pr_rec_cap = 0;   // offsets
 
     bool poisoned = false;
     std::string last_error;
@@ -408,7 +411,7 @@ void comm_release(kh_ctx *c);
 // ---- format.hip
 void text_release(kh_ctx *c);  // kh_destroy: the text stream's buffers and events
 // ---- profile.hip
-void profile_release(kh_ctx *c);  // kh_destroy: the chunk buffers and events of kh_profile
+void profile_release(kh_ctx *c);  // kh_destroy: the chunk buffers and events of kh_profile, the rows of kh_profile_records
 
 // ---- stage timing: HIP events on the launch stream, resolved lazily ---------------------------
 struct StageTimer {

@@ -22,6 +22,8 @@ static const char *USAGE =
     "Usage: kmerust [OPTIONS] <K> [PATH]\n"
     "       kmerust query <INDEX> <KMER>\n"
     "       kmerust query <INDEX> --sequences <PATH> [-i <INPUT_FORMAT>] [-Q <MIN_QUALITY>] [-f summary|profile] [-q]\n"
+    "       kmerust filter <INDEX> <PATH> [-i <INPUT_FORMAT>] [-Q <MIN_QUALITY>] [--min-count <LO>] [--max-count <HI>]\n"
+    "                      [--min-kmers <N>] [--min-fraction <F>] [-v] [-q]\n"
     "\n"
     "Arguments:\n"
     "  <K>     K-mer length (1-32)\n"
@@ -40,6 +42,14 @@ static const char *USAGE =
     "query --sequences: the index's count of the k-mer at every base of the sequences in <PATH>, one line per record.\n"
     "  -f summary (default)  {record}\\t{windows}\\t{present}\\t{min}\\t{max}\\t{sum}\n"
     "  -f profile            one count per window start, '-' where there is no k-mer (N, soft mask, low quality)\n"
+    "\n"
+    "filter: the records of <PATH> with at least N k-mers (and a share F of their k-mers) whose count in the index is in LO..HI,\n"
+    "  written as they were read (FASTA or FASTQ); {records}\\t{kept} on stderr.\n"
+    "      --min-count <LO>               Lowest count that is in range [default: 1]\n"
+    "      --max-count <HI>               Highest count that is in range [default: 4294967294]\n"
+    "      --min-kmers <N>                K-mers in range a record needs [default: 1]\n"
+    "      --min-fraction <F>             ... and their share of the record's k-mers, 0-1 [default: 0]\n"
+    "  -v, --invert                       Write the records the rule drops instead\n"
     "\n"
     "  -h, --help                         Print help\n"
     "  -V, --version                      Print version\n";
@@ -155,6 +165,103 @@ static int run_query_sequences(int argc, char **argv) {
     return 0;
 }
 
+// kmerust filter <INDEX> <PATH> [-i FMT] [-Q N] [--min-count LO] [--max-count HI] [--min-kmers N] [--min-fraction F] [-v] [-q]:
+// reads kept or dropped by the abundance of their k-mers in the index (no reference counterpart)
+static int run_filter(int argc, char **argv) {
+    std::string index, path;
+    bool have_index = false, have_path = false, quiet = false;
+    SequenceFormat in_fmt = SequenceFormat::Auto;
+    FilterRule rule;
+    int min_quality = -1;
+    size_t batch_bytes = 0;
+    auto value_of = [&](int &i, const std::string &arg, const char *name) -> std::string {
+        const size_t eq = arg.find('=');
+        if (arg.rfind("--", 0) == 0 && eq != std::string::npos) return arg.substr(eq + 1);
+        if (arg.rfind("--", 0) != 0 && arg.size() > 2) return arg.substr(2);  // -QVALUE
+        if (i + 1 >= argc) usage_error(std::string("a value is required for '") + name + "' but none was supplied");
+        return argv[++i];
+    };
+    for (int i = 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        const std::string key = a.rfind("--", 0) == 0 ? a.substr(0, a.find('=')) : a.substr(0, 2);
+        if (a == "-q" || a == "--quiet") {
+            quiet = true;
+        } else if (a == "-v" || a == "--invert") {
+            rule.invert = true;
+        } else if (key == "-i" || key == "--input-format") {
+            const std::string v = value_of(i, a, "--input-format <INPUT_FORMAT>");
+            if (v == "auto") in_fmt = SequenceFormat::Auto;
+            else if (v == "fasta") in_fmt = SequenceFormat::Fasta;
+            else if (v == "fastq") in_fmt = SequenceFormat::Fastq;
+            else usage_error("invalid value '" + v + "' for '--input-format <INPUT_FORMAT>'\n  [possible values: auto, fasta, fastq]");
+        } else if (key == "-Q" || key == "--min-quality") {
+            min_quality = (int)parse_u64(value_of(i, a, "--min-quality <MIN_QUALITY>"), "--min-quality <MIN_QUALITY>", 255);
+        } else if (key == "--min-count") {
+            rule.min_count = (uint32_t)parse_u64(value_of(i, a, "--min-count <LO>"), "--min-count <LO>", 0xFFFFFFFFull);
+        } else if (key == "--max-count") {
+            rule.max_count = (uint32_t)parse_u64(value_of(i, a, "--max-count <HI>"), "--max-count <HI>", 0xFFFFFFFFull);
+        } else if (key == "--min-kmers") {
+            rule.min_kmers = parse_u64(value_of(i, a, "--min-kmers <N>"), "--min-kmers <N>", UINT64_MAX);
+        } else if (key == "--min-fraction") {
+            const std::string v = value_of(i, a, "--min-fraction <F>");
+            char *end = nullptr;
+            const double f = v.empty() ? -1.0 : strtod(v.c_str(), &end);
+            if (v.empty() || *end || v.find_first_not_of("0123456789.eE+-") != std::string::npos)
+                usage_error("invalid value '" + v + "' for '--min-fraction <F>': invalid float literal");
+            if (!(f >= 0.0 && f <= 1.0)) usage_error("invalid value '" + v + "' for '--min-fraction <F>': must be between 0 and 1");
+            rule.min_fraction = f;
+        } else if (key == "--__batch-kb") {  // hidden test hook, as for query --sequences
+            batch_bytes = (size_t)parse_u64(value_of(i, a, "--__batch-kb <N>"), "--__batch-kb <N>", 1u << 22) << 10;
+        } else if (a.size() > 1 && a[0] == '-' && a != "-") {
+            usage_error("unexpected argument '" + a + "' found");
+        } else if (!have_index) {
+            index = a;
+            have_index = true;
+        } else if (!have_path) {
+            path = a;
+            have_path = true;
+        } else {
+            usage_error("unexpected argument '" + a + "' found");
+        }
+    }
+    if (!have_index) usage_error("the following required arguments were not provided:\n  <INDEX>\n  <PATH>\n\nUsage: kmerust filter <INDEX> <PATH>");
+    if (!have_path) usage_error("the following required arguments were not provided:\n  <PATH>\n\nUsage: kmerust filter <INDEX> <PATH>");
+    const bool from_stdin = is_stdin_path(path);
+    if (!from_stdin) {
+        struct stat st;
+        if (stat(path.c_str(), &st) != 0) {
+            fprintf(stderr, "Problem with arguments:\n File not found: %s\n", path.c_str());
+            return 1;
+        }
+    }
+    const SequenceFormat resolved = resolve_format(in_fmt, from_stdin ? nullptr : &path);
+    if (!quiet) {  // (the banner of query --sequences, with the rule where that has the output format)
+        fprintf(stderr, "index: %s\n", index.c_str());
+        fprintf(stderr, "data: %s\n", from_stdin ? "<stdin>" : path.c_str());
+        if (in_fmt == SequenceFormat::Auto) fprintf(stderr, "input-format: %s (auto-detected)\n", format_name(resolved));
+        else fprintf(stderr, "input-format: %s\n", format_name(in_fmt));
+        fprintf(stderr, "reader: kmerhip\n");
+        fprintf(stderr, "keep: %s%llu k-mers and %g of the record's with a count in %u..%u\n", rule.invert ? "fewer than " : "at least ",
+                (unsigned long long)rule.min_kmers, rule.min_fraction, rule.min_count, rule.max_count);
+        if (min_quality >= 0) fprintf(stderr, "min-quality: %d\n", min_quality);
+        fprintf(stderr, "\n");
+    }
+    if (min_quality >= 0 && resolved == SequenceFormat::Fasta) fprintf(stderr, "warning: --min-quality is ignored for FASTA input\n");
+    if (min_quality >= 0 && from_stdin) fprintf(stderr, "warning: --min-quality is not yet supported for stdin input\n");
+#if !defined(__SANITIZE_ADDRESS__) && !defined(KMERUST_UNDER_ASAN) && !defined(KMERUST_ALWAYS_CLEAN_EXIT)  // (as cli_main)
+    leak_at_exit() = !getenv("KMERUST_CLEAN_EXIT");
+#endif
+    try {
+        uint64_t records = 0, kept = 0;
+        filter_sequences(index, path, in_fmt, min_quality, rule, stdout, &records, &kept, batch_bytes);
+        if (!quiet) fprintf(stderr, "%llu\t%llu\n", (unsigned long long)records, (unsigned long long)kept);
+    } catch (const Error &e) {
+        fprintf(stderr, "Application error:\n %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 static int run_query(int argc, char **argv) {
     for (int i = 2; i < argc; ++i)
         if (!strncmp(argv[i], "--sequences", 11) && (argv[i][11] == 0 || argv[i][11] == '=')) return run_query_sequences(argc, argv);
@@ -220,6 +327,7 @@ static int run_parse_dump(int argc, char **argv) {
 
 int cli_main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "query")) return run_query(argc, argv);  // src/main.rs:39-47
+    if (argc > 1 && !strcmp(argv[1], "filter")) return run_filter(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "__parse")) return run_parse_dump(argc, argv);
 
     std::string k_arg, path = "-", save;

@@ -25,6 +25,7 @@
 // ... and so are the entry points of `query --sequences`: without them the command refuses cleanly instead of failing to link.
 #pragma weak kh_profile
 #pragma weak kh_merge_pairs
+#pragma weak kh_profile_records
 
 namespace kmerust {
 
@@ -133,8 +134,12 @@ struct BatchBuilder {
     bool want_qual;
     size_t limit;
     const BatchSink &sink;
+    bool keep_text;
     uint64_t total_records = 0;
-    BatchBuilder(bool wq, size_t lim, const BatchSink &s) : want_qual(wq), limit(lim), sink(s) {}
+    BatchBuilder(bool wq, size_t lim, const BatchSink &s, bool kt = false) : want_qual(wq), limit(lim), sink(s), keep_text(kt) {}
+    void header(const std::string &line) {
+        if (keep_text) b.headers.emplace_back(line, 1);
+    }
     void end_record() {
         b.bases.push_back('\n');
         if (want_qual) b.qual.push_back('\n');
@@ -146,6 +151,7 @@ struct BatchBuilder {
         if (b.records) sink(b);
         b.bases.clear();
         b.qual.clear();
+        b.headers.clear();
         b.records = 0;
     }
 };
@@ -153,12 +159,13 @@ struct BatchBuilder {
 }  // namespace
 
 uint64_t read_sequences(const std::string &path, SequenceFormat fmt, bool want_qual, size_t batch_bytes,
-                        const BatchSink &sink) {
+                        const BatchSink &sink, bool keep_text) {
     const SequenceFormat f = resolve_format(fmt, is_stdin_path(path) ? nullptr : &path);
     LineSource src(path);
     const bool fastq = f == SequenceFormat::Fastq;
+    if (fastq && keep_text) want_qual = true;  // (the caller writes the records out again)
     if (!fastq) want_qual = false;  // FASTA carries no qualities (reader.rs:68-79)
-    BatchBuilder bb(want_qual, batch_bytes, sink);
+    BatchBuilder bb(want_qual, batch_bytes, sink, keep_text);
     std::string line;
     if (!fastq) {
         bool in_record = false;
@@ -166,6 +173,7 @@ uint64_t read_sequences(const std::string &path, SequenceFormat fmt, bool want_q
             if (!line.empty() && line[0] == '>') {
                 if (in_record) bb.end_record();
                 in_record = true;
+                bb.header(line);
             } else if (!in_record) {
                 if (line.empty()) continue;
                 throw Error("failed to parse sequence record: expected '>' at record start");
@@ -182,6 +190,7 @@ uint64_t read_sequences(const std::string &path, SequenceFormat fmt, bool want_q
                 continue;
             }
             if (line[0] != '@') throw Error("failed to parse sequence record: expected '@' at record start");
+            bb.header(line);
             const size_t seq_start = bb.b.bases.size();
             bool plus = false;
             while ((have = src.next(line))) {
@@ -1102,38 +1111,147 @@ uint64_t write_profile_lines(FILE *out, const uint8_t *bases, const uint32_t *pr
     return records;
 }
 
+std::vector<uint64_t> record_starts(const uint8_t *bases, size_t n) {
+    std::vector<uint64_t> rs;
+    for (size_t s = 0; s < n;) {
+        rs.push_back(s);
+        const void *nl = memchr(bases + s, '\n', n - s);
+        s = nl ? (size_t)((const uint8_t *)nl - bases) + 1 : n;
+    }
+    rs.push_back(n);
+    return rs;
+}
+
+void write_summary_rows(FILE *out, const uint32_t *rows, uint64_t nrec, uint64_t first_ordinal) {
+    OutBuf w(out);
+    for (uint64_t r = 0; r < nrec; ++r) {
+        const uint32_t *row = rows + r * KH_REC_WORDS;
+        w.put_u64(first_ordinal + r); w.put("\t", 1);
+        w.put_u64(row[KH_REC_WINDOWS]); w.put("\t", 1);
+        w.put_u64(row[KH_REC_PRESENT]); w.put("\t", 1);
+        w.put_u64(row[KH_REC_MIN]); w.put("\t", 1);
+        w.put_u64(row[KH_REC_MAX]); w.put("\t", 1);
+        w.put_u64((uint64_t)row[KH_REC_SUM_LO] | ((uint64_t)row[KH_REC_SUM_HI] << 32)); w.put("\n", 1);
+    }
+}
+
+namespace {
+// The index as a device table: what `query --sequences` and `filter` read.
+struct IndexTable {
+    kh_ctx *c = nullptr;
+    uint32_t k = 0;
+    IndexTable(const std::string &index_path, int min_quality) {
+        const PackedCounts idx = load_index(index_path);
+        kh_config cfg;
+        memset(&cfg, 0, sizeof(cfg));
+        cfg.struct_size = sizeof(cfg);
+        cfg.k = k = idx.k;
+        cfg.min_quality = min_quality;
+        cfg.device = -1;
+        cfg.capacity_hint = idx.keys.size();
+        Session::check_on(nullptr, kh_create(&c, &cfg), "kh_create");
+        try {
+            Session::check_on(c, kh_merge_pairs(c, idx.keys.data(), idx.counts.data(), idx.keys.size()), "kh_merge_pairs");
+        } catch (...) {
+            kh_destroy(c);
+            throw;
+        }
+    }
+    ~IndexTable() {
+        if (c && !leak_at_exit()) kh_destroy(c);
+    }
+};
+}  // namespace
+
 void query_sequences(const std::string &index_path, const std::string &path, SequenceFormat fmt, int min_quality, ProfileFormat out_fmt,
                      FILE *out, size_t batch_bytes) {
     if (!kh_profile || !kh_merge_pairs)
         throw Error("query --sequences needs a kmerhip library with kh_profile and kh_merge_pairs; the one this program was built against has neither");
-    const PackedCounts idx = load_index(index_path);
     const SequenceFormat resolved = resolve_format(fmt, is_stdin_path(path) ? nullptr : &path);
     const bool want_qual = min_quality >= 0 && resolved == SequenceFormat::Fastq && !is_stdin_path(path);  // as counting: wants_quality()
-    kh_config cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.struct_size = sizeof(cfg);
-    cfg.k = idx.k;
-    cfg.min_quality = want_qual ? min_quality : -1;
-    cfg.device = -1;
-    cfg.capacity_hint = idx.keys.size();
-    struct Ctx {
-        kh_ctx *c = nullptr;
-        ~Ctx() {
-            if (c && !leak_at_exit()) kh_destroy(c);
-        }
-    } ctx;
-    Session::check_on(nullptr, kh_create(&ctx.c, &cfg), "kh_create");
-    Session::check_on(ctx.c, kh_merge_pairs(ctx.c, idx.keys.data(), idx.counts.data(), idx.keys.size()), "kh_merge_pairs");
+    IndexTable ctx(index_path, want_qual ? min_quality : -1);
     const size_t batch = batch_bytes ? batch_bytes : (size_t)16 << 20;  // bytes of flat records per kh_profile call
     std::vector<uint32_t> prof;
     uint64_t ordinal = 0;
+    // the summary's six numbers per record come reduced from the device, unless the parent's route is asked for
+    const char *host_summary = getenv("KMERUST_HOST_SUMMARY");
+    const bool device_summary = out_fmt == ProfileFormat::Summary && kh_profile_records && !(host_summary && host_summary[0] && host_summary[0] != '0');
     read_sequences(path, fmt, want_qual, batch, [&](const Batch &b) {
+        if (device_summary) {
+            const std::vector<uint64_t> rs = record_starts(b.bases.data(), b.bases.size());
+            const uint64_t nrec = rs.size() - 1;
+            prof.resize(nrec * KH_REC_WORDS);
+            Session::check_on(ctx.c, kh_profile_records(ctx.c, b.bases.data(), want_qual && !b.qual.empty() ? b.qual.data() : nullptr, b.bases.size(),
+                                                        rs.data(), nrec, 1, 0xFFFFFFFEu, prof.data()),
+                              "kh_profile_records");
+            write_summary_rows(out, prof.data(), nrec, ordinal);
+            ordinal += nrec;
+            return;
+        }
         prof.resize(b.bases.size());
         Session::check_on(ctx.c, kh_profile(ctx.c, b.bases.data(), want_qual && !b.qual.empty() ? b.qual.data() : nullptr, b.bases.size(), prof.data()),
                           "kh_profile");
-        ordinal += write_profile_lines(out, b.bases.data(), prof.data(), b.bases.size(), idx.k, out_fmt, ordinal);
+        ordinal += write_profile_lines(out, b.bases.data(), prof.data(), b.bases.size(), ctx.k, out_fmt, ordinal);
     });
     if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+}
+
+// =============================================================================================
+// reads kept or dropped by their k-mers' abundance
+// =============================================================================================
+bool filter_keeps(const uint32_t *row, const FilterRule &rule) {
+    const uint32_t windows = row[KH_REC_WINDOWS], in_range = row[KH_REC_IN_RANGE];
+    return windows > 0 && in_range >= rule.min_kmers && (double)in_range >= rule.min_fraction * (double)windows;
+}
+
+void append_record(std::string &dst, const std::string &header, const uint8_t *seq, size_t len, const uint8_t *qual) {
+    dst.push_back(qual ? '@' : '>');
+    dst += header;
+    dst.push_back('\n');
+    dst.append(reinterpret_cast<const char *>(seq), len);
+    dst.push_back('\n');
+    if (qual) {
+        dst += "+\n";
+        dst.append(reinterpret_cast<const char *>(qual), len);
+        dst.push_back('\n');
+    }
+}
+
+void filter_sequences(const std::string &index_path, const std::string &path, SequenceFormat fmt, int min_quality, const FilterRule &rule,
+                      FILE *out, uint64_t *records, uint64_t *kept, size_t batch_bytes) {
+    if (!kh_profile_records || !kh_merge_pairs)
+        throw Error("filter needs a kmerhip library with kh_profile_records and kh_merge_pairs; the one this program was built against has neither");
+    const SequenceFormat resolved = resolve_format(fmt, is_stdin_path(path) ? nullptr : &path);
+    const bool fastq = resolved == SequenceFormat::Fastq;
+    const bool mask = min_quality >= 0 && fastq && !is_stdin_path(path);  // as counting: wants_quality()
+    IndexTable ctx(index_path, mask ? min_quality : -1);
+    const size_t batch = batch_bytes ? batch_bytes : (size_t)16 << 20;
+    std::vector<uint32_t> rows;
+    std::string text;
+    uint64_t nseen = 0, nkept = 0;
+    read_sequences(path, fmt, false, batch, [&](const Batch &b) {
+        const std::vector<uint64_t> rs = record_starts(b.bases.data(), b.bases.size());
+        const uint64_t nrec = rs.size() - 1;
+        if (nrec != b.headers.size()) throw Error("internal error: the reader's records and headers disagree");
+        rows.resize(nrec * KH_REC_WORDS);
+        // (the qualities are there to be written out again; they mask on the device only with -Q)
+        Session::check_on(ctx.c, kh_profile_records(ctx.c, b.bases.data(), mask ? b.qual.data() : nullptr, b.bases.size(), rs.data(), nrec,
+                                                    rule.min_count, rule.max_count, rows.data()),
+                          "kh_profile_records");
+        text.clear();
+        for (uint64_t r = 0; r < nrec; ++r) {
+            if (filter_keeps(rows.data() + r * KH_REC_WORDS, rule) == rule.invert) continue;
+            const size_t s = (size_t)rs[r], len = (size_t)rs[r + 1] - s - 1;  // (every record of the reader ends in '\n')
+            append_record(text, b.headers[r], b.bases.data() + s, len, fastq ? b.qual.data() + s : nullptr);
+            ++nkept;
+        }
+        nseen += nrec;
+        if (!text.empty() && fwrite(text.data(), 1, text.size(), out) != text.size())
+            throw Error(std::string("failed to write output: ") + std::strerror(errno));
+    }, true);
+    if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+    if (records) *records = nseen;
+    if (kept) *kept = nkept;
 }
 
 void write_counts(FILE *out, const PackedCounts &pc, OutputFormat fmt, uint64_t min_count) {

@@ -51,13 +51,16 @@ inline bool is_stdin_path(const std::string &p) { return p == "-"; }      // src
 // listed in DESIGN.md: lines are right-trimmed of CR / blanks, FASTA sequence lines are
 // concatenated, FASTQ records may wrap over several lines, a record header must start with '>' /
 // '@', and a FASTQ quality string must be as long as its sequence.
+// keep_text (for a caller that writes records out again, `kmerust filter`): `headers` holds every record's header line without
+// its '>' / '@', and the qualities of a FASTQ file are kept whether want_qual or not.  Off, a Batch is what it always was.
 struct Batch {
     std::vector<uint8_t> bases, qual;
     uint64_t records = 0;
+    std::vector<std::string> headers;  // filled only with keep_text
 };
 using BatchSink = std::function<void(const Batch &)>;
 uint64_t read_sequences(const std::string &path, SequenceFormat fmt, bool want_qual, size_t batch_bytes,
-                        const BatchSink &sink);
+                        const BatchSink &sink, bool keep_text = false);
 
 // ---- counting --------------------------------------------------------------------------------
 struct PackedCounts {
@@ -143,11 +146,34 @@ enum class ProfileFormat { Summary, Profile };
 // Records are numbered from first_ordinal; returns the number of records written.
 uint64_t write_profile_lines(FILE *out, const uint8_t *bases, const uint32_t *profile, size_t n, uint32_t k, ProfileFormat fmt,
                              uint64_t first_ordinal);
-// load_index, the pairs into a device table (kh_merge_pairs), then kh_profile per batch of read_sequences and the lines above.
-// min_quality: -1 = none; used for FASTQ files only, as in counting.  batch_bytes: flat record bytes per kh_profile call (0 = 16 MiB).
+// The records of a flat batch as kh_profile_records takes them: the start byte of every '\n'-terminated run, and n behind the last
+// (nrec + 1 entries; an unterminated last run is a record, as for write_profile_lines).
+std::vector<uint64_t> record_starts(const uint8_t *bases, size_t n);
+// The Summary lines from the rows of kh_profile_records (KH_REC_WORDS words per record): the same bytes as write_profile_lines.
+void write_summary_rows(FILE *out, const uint32_t *rows, uint64_t nrec, uint64_t first_ordinal);
+// load_index, the pairs into a device table (kh_merge_pairs), then per batch of read_sequences: Summary from kh_profile_records (the
+// reduction runs on the device; KMERUST_HOST_SUMMARY=1, or a library without that call, keeps kh_profile + write_profile_lines),
+// Profile from kh_profile and the lines above.
+// min_quality: -1 = none; used for FASTQ files only, as in counting.  batch_bytes: flat record bytes per call (0 = 16 MiB).
 // Throws Error.
 void query_sequences(const std::string &index_path, const std::string &path, SequenceFormat fmt, int min_quality, ProfileFormat out_fmt,
                      FILE *out, size_t batch_bytes = 0);
+
+// ---- reads kept or dropped by their k-mers' abundance (`kmerust filter <INDEX> <PATH>`; no reference counterpart) ----------------
+struct FilterRule {
+    uint32_t min_count = 1, max_count = 0xFFFFFFFEu;  // a window is in range when min_count <= count <= max_count
+    uint64_t min_kmers = 1;                           // windows in range a record needs ...
+    double min_fraction = 0.0;                        // ... and their share of the record's windows
+    bool invert = false;                              // write the records the rule drops
+};
+// row: one row of kh_profile_records.  windows > 0 && in_range >= min_kmers && in_range >= min_fraction * windows (invert is the writer's)
+bool filter_keeps(const uint32_t *row, const FilterRule &rule);
+// ">{header}\n{sequence}\n", or with qual "@{header}\n{sequence}\n+\n{quality}\n", appended to dst
+void append_record(std::string &dst, const std::string &header, const uint8_t *seq, size_t len, const uint8_t *qual);
+// load_index into a device table, then per batch of read_sequences one kh_profile_records call and the records the rule keeps, in input
+// order, to out.  min_quality masks on the device (FASTQ files only, as in counting).  Throws Error.
+void filter_sequences(const std::string &index_path, const std::string &path, SequenceFormat fmt, int min_quality, const FilterRule &rule,
+                      FILE *out, uint64_t *records, uint64_t *kept, size_t batch_bytes = 0);
 
 // ---- KMIX index (src/index.rs) -----------------------------------------------------------------
 uint32_t crc32_ieee(const uint8_t *data, size_t n, uint32_t crc = 0);  // src/index.rs:404-431

@@ -27,6 +27,9 @@ KH_ERR_PEER = -11
 TEXT_FASTA, TEXT_FASTQ = 1, 2
 KH_OUT_FASTA, KH_OUT_TSV, KH_OUT_JSON = 1, 2, 3  # kh_result_text_begin
 PROFILE_NO_WINDOW = 0xFFFFFFFF  # KH_PROFILE_NO_WINDOW: an entry of kh_profile* where counting would see no window
+# KH_REC_*: the words of a row of kh_profile_records*
+REC_WORDS = 8
+REC_WINDOWS, REC_PRESENT, REC_IN_RANGE, REC_MIN, REC_MAX, REC_SUM_LO, REC_SUM_HI, REC_FIRST_LOW = range(8)
 
 
 class KhConfig(C.Structure):
@@ -84,6 +87,8 @@ SYMBOLS = {
     "kh_lookup": (C.c_int, [_P, _P, _U64, _P]),
     "kh_profile_device": (C.c_int, [_P, _P, _P, _U64, _P]),
     "kh_profile": (C.c_int, [_P, _P, _P, _U64, _P]),
+    "kh_profile_records_device": (C.c_int, [_P, _P, _P, _U64, _P, _U64, C.c_uint32, C.c_uint32, _P]),
+    "kh_profile_records": (C.c_int, [_P, _P, _P, _U64, _P, _U64, C.c_uint32, C.c_uint32, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
     "kh_set_shard": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "kh_set_region_window": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -396,6 +401,34 @@ class DeviceCounter:
         uint32 entries to fill, or torch tensors on this context's device.  Returns when d_out is complete."""
         ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
         self._check(lib().kh_profile_device(self._h, ptr(d_bases), ptr(d_qual), int(n), ptr(d_out)))
+
+    def profile_records(self, bases, rec_start, qual=None, lo=1, hi=0xFFFFFFFE, out=None):
+        """The profile of `bases` reduced per record on the device: rec_start holds nrec + 1 ascending offsets into the flat
+        buffer (record r owns the window starts rec_start[r] .. rec_start[r+1]; the last offset <= len(bases)).  Returns an
+        (nrec, 8) uint32 array, columns REC_WINDOWS .. REC_FIRST_LOW: windows, present (count > 0), in_range (lo <= count <= hi),
+        min, max, the sum's low and high word, and the offset of the first window with a count < lo (0xFFFFFFFF: none)."""
+        bp, kb = _addr(bases)
+        n = kb.size if kb is not None else 0
+        qp, kq = _addr(qual)
+        if kq is not None and kq.size != n:
+            raise ValueError("qual must have the same length as bases")
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        if rs.ndim != 1 or rs.size < 1:
+            raise ValueError("rec_start needs nrec + 1 offsets")
+        nrec = rs.size - 1
+        if out is None:
+            out = np.empty((nrec, REC_WORDS), dtype=np.uint32)
+        assert out.dtype == np.uint32 and out.flags.c_contiguous and out.flags.writeable and out.size >= nrec * REC_WORDS
+        self._check(lib().kh_profile_records(self._h, bp, qp, n, rs.ctypes.data, nrec, int(lo), int(hi), out.ctypes.data))
+        return out.reshape(-1)[:nrec * REC_WORDS].reshape(nrec, REC_WORDS)
+
+    def profile_records_device(self, d_bases, d_qual, n, d_rec_start, nrec, d_rows, lo=1, hi=0xFFFFFFFE):
+        """The same on device memory: integer addresses or torch tensors of n bases, n quality bytes or None, nrec + 1 uint64
+        offsets and nrec * 8 uint32 words to fill.  The offsets are the caller's contract (not checked).  Returns when d_rows
+        is complete."""
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        self._check(lib().kh_profile_records_device(self._h, ptr(d_bases), ptr(d_qual), int(n), ptr(d_rec_start), int(nrec), int(lo),
+                                                    int(hi), ptr(d_rows)))
 
     # -- multi-GPU merge ---------------------------------------------------
     def comm_init(self, nranks, rank, unique_id):

@@ -13,7 +13,13 @@ For k = 21 and for k = 31 with -Q 20, on synthetic 150 bp reads (kh_synth_reads_
      same size (KMERHIP_PATH=direct, kh_stats.stage_ms[direct]), and kh_lookup fed the canonical keys of the windows of the
      first --lookup-reads reads from host memory (s, M keys/s)
 and the two ratios: a / direct count (expected <= 1.05), and kh_lookup's time over kh_profile's on the same reads (leg d_lookup
-times both from pageable memory; expected > 1)."""
+times both from pageable memory; expected > 1).
+The per-record reduction (kh_profile_records*), k = 21 only, every figure the median of 5 runs after the context's first call,
+with the spread (max - min) of the runs beside it:
+  r_host  the summary's route before kh_profile_records -- kh_profile into host memory plus the six numbers per record folded on
+          one host thread (numpy here: segment sums over the profile) -- against kh_profile_records from pageable and from pinned
+          memory, on the same reads
+  r_dev   the kernels alone: kh_profile_device against kh_profile_records_device"""
 import argparse
 import json
 import os
@@ -100,6 +106,55 @@ def leg(args):
                     res["pinned"] = {"s": s, "gb_per_s_in": n * (2 if minq is not None else 1) / s / 1e9, "gb_per_s_out": 4 * n / s / 1e9, "m_entries_per_s": n / s / 1e6}
                     assert np.array_equal(po.array, ho)
                 out.update(res)
+    elif args.leg in ("r_host", "r_dev"):
+        def med5(f):
+            f()                                     # the context's first call of this kind: buffers
+            ts = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                f()
+                ts.append(time.perf_counter() - t0)
+            ts.sort()
+            return {"median_s": ts[2], "spread_s": ts[-1] - ts[0]}
+        nrec = args.reads
+        rs = np.arange(nrec + 1, dtype=np.uint64) * np.uint64(151)
+        with native.DeviceCounter(k, min_quality=minq) as dc:
+            dc.push_device(tb.data_ptr(), q, n)
+            dc.finish()
+            if args.leg == "r_dev":
+                to = torch.empty(n, dtype=torch.int32, device="cuda:0")
+                trs = torch.from_numpy(rs.view(np.int64)).to("cuda:0")
+                trows = torch.empty(nrec * 8, dtype=torch.int32, device="cuda:0")
+                out["profile_device"] = med5(lambda: dc.profile_device(tb.data_ptr(), q, n, to.data_ptr()))
+                out["profile_records_device"] = med5(lambda: dc.profile_records_device(tb.data_ptr(), q, n, trs, nrec, trows))
+                rows = trows.cpu().numpy().view(np.uint32).reshape(nrec, 8)
+                res = to.cpu().numpy().view(np.uint32)
+                win = res != 0xFFFFFFFF
+                assert int(rows[:, 0].sum()) == int(win.sum()) and int(rows[:, 1].sum()) == int((win & (res > 0)).sum())
+            else:
+                hb = tb.cpu().numpy()
+                hq = tq.cpu().numpy() if minq is not None else None
+                ho = np.empty(n, dtype=np.uint32)
+                hrows = np.empty((nrec, 8), dtype=np.uint32)
+
+                def host_summary():   # (a stand-in for the CLI's write_profile_lines: vectorised, and no formatting)
+                    dc.profile(hb, hq, out=ho)
+                    P = ho.reshape(nrec, 151)
+                    w = P != 0xFFFFFFFF
+                    v = np.where(w, P, 0)
+                    return w.sum(axis=1), (v > 0).sum(axis=1), np.where(w, P, 0xFFFFFFFF).min(axis=1), v.max(axis=1), v.sum(axis=1, dtype=np.uint64)
+                out["profile_plus_host_summary"] = med5(host_summary)
+                out["profile_alone"] = med5(lambda: dc.profile(hb, hq, out=ho))
+                out["profile_records_pageable"] = med5(lambda: dc.profile_records(hb, rs, hq, out=hrows))
+                ref = host_summary()
+                assert np.array_equal(hrows[:, 0], ref[0]) and np.array_equal(hrows[:, 1], ref[1]) and np.array_equal(hrows[:, 4], ref[3])
+                with native.PinnedArray(n) as pb, native.PinnedArray(n) as pq, native.PinnedArray(nrec * 8, dtype=np.uint32) as po:
+                    pb.array[:] = hb
+                    if hq is not None:
+                        pq.array[:] = hq
+                    out["profile_records_pinned"] = med5(lambda: dc.profile_records(pb.array, rs, pq.array if hq is not None else None, out=po.array))
+                    assert np.array_equal(po.array.reshape(nrec, 8), hrows)
+                out["bytes_back_per_record"] = {"profile": 604, "profile_records": 32}
     elif args.leg == "d_count":
         # the direct counting kernel over the same buffer into a table of the size leg a's table has
         with native.DeviceCounter(k, min_quality=minq) as dc:
@@ -138,10 +193,29 @@ def main():
     ap.add_argument("--leg")
     ap.add_argument("--k", type=int, default=21)
     ap.add_argument("--minq", type=int, default=-1)
-    ap.add_argument("--timeout", type=int, default=240)
+    ap.add_argument("--timeout", type=int, help="seconds per leg (default 240; 900 with --records-only: r_host makes some 30 calls over all reads)")
+    ap.add_argument("--records-only", action="store_true", help="only the legs of the per-record reduction (r_host, r_dev), k = 21")
     args = ap.parse_args()
+    if args.timeout is None:
+        args.timeout = 900 if args.records_only else 240
     if args.leg:
         return leg(args)
+    if args.records_only:
+        report = {"tool": "tools/profile_probe.py --records-only", "reads": args.reads, "read_len": 150, "k": 21}
+        for name in ("r_dev", "r_host"):
+            cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--k", "21", "--minq", "-1", "--reads", str(args.reads)]
+            try:
+                p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
+                lines = [l for l in p.stdout.splitlines() if l.startswith("LEG ")]
+                report[name] = json.loads(lines[-1][4:]) if p.returncode == 0 and lines else {"error": f"exit {p.returncode}", "stderr": p.stderr[-600:]}
+            except subprocess.TimeoutExpired:
+                report[name] = {"error": f"timeout after {args.timeout} s"}
+            if "error" in report[name]:
+                report["stopped"] = f"leg {name} failed: nothing more is started on the device"
+                print(json.dumps(report, indent=1))
+                return 1
+        print(json.dumps(report, indent=1))
+        return 0
     report = {"tool": "tools/profile_probe.py", "reads": args.reads, "read_len": 150, "configs": []}
     for k, minq in ((21, -1), (31, 20)):
         cfg = {"k": k, "min_quality": None if minq < 0 else minq}
