@@ -187,10 +187,15 @@ int kh_host_unregister(void *p);
 int kh_result_size(kh_ctx *ctx, uint64_t min_count, uint64_t *n);
 /* Copy (packed canonical key, count) pairs with count >= min_count into
  * caller arrays of capacity cap; order unspecified (HashMap iteration order is
- * unspecified in the reference too).  *n receives the number written. */
+ * unspecified in the reference too).  *n receives the number written.
+ *   - A cap smaller than kh_result_size(min_count): KH_ERR_RANGE, *n = 0 and NOTHING is written to keys / counts (the
+ *     size is taken first); the context stays usable.  min_count = 0 selects what 1 selects.  cap = 0 takes NULL arrays. */
 int kh_result_copy(kh_ctx *ctx, uint64_t *keys, uint64_t *counts, uint64_t cap,
                    uint64_t min_count, uint64_t *n);
-/* Same into device arrays (for the multi-GPU exchange and device consumers). */
+/* Same into device arrays (for the multi-GPU exchange and device consumers).
+ *   - A cap smaller than the number of pairs: KH_ERR_RANGE, *n = cap, and exactly cap pairs ARE written -- distinct pairs
+ *     of the result with their counts, which ones is unspecified -- and nothing at or behind d_keys[cap] / d_counts[cap];
+ *     the context stays usable.  (One pass over the table: the size is known only when the pairs are out.) */
 int kh_result_copy_device(kh_ctx *ctx, uint64_t *d_keys, uint64_t *d_counts, uint64_t cap,
                           uint64_t min_count, uint64_t *n);
 /* The same result as TEXT, formatted on the device: replaces output_counts (src/run.rs:441-486) -- unpacking, the decimal
@@ -223,7 +228,10 @@ int kh_result_text_begin(kh_ctx *ctx, uint32_t format, uint64_t min_count, uint6
 int kh_result_text_next(kh_ctx *ctx, uint8_t *buf, uint64_t cap, uint64_t *n);
 int kh_result_text_next_device(kh_ctx *ctx, uint8_t *d_buf, uint64_t cap, uint64_t *n);
 /* Count-of-counts after the min_count filter, ascending by count
- * (compute_histogram, src/histogram.rs:88-94 as used by run.rs:471-481). */
+ * (compute_histogram, src/histogram.rs:88-94 as used by run.rs:471-481).  *n receives the number of lines written.
+ *   - A cap smaller than the number of lines: KH_ERR_RANGE, *n = cap, and count / freq hold the FIRST cap lines (the
+ *     ascending prefix of the whole histogram), nothing at or behind entry cap; the context stays usable -- call again
+ *     with more room (the number of lines is not reported: grow cap until KH_OK).  cap = 0 takes NULL arrays. */
 int kh_histogram(kh_ctx *ctx, uint64_t min_count, uint64_t *count, uint64_t *freq,
                  uint64_t cap, uint64_t *n);
 /* counts[i] = count of packed canonical key keys[i], 0 if absent
