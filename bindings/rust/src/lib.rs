@@ -108,6 +108,12 @@ pub mod sys {
                                          nrec: u64, lo: u32, hi: u32, d_rows: *mut u32) -> c_int;
         pub fn kh_profile_records(ctx: *mut KhCtx, bases: *const u8, qual: *const u8, n: u64, rec_start: *const u64, nrec: u64,
                                   lo: u32, hi: u32, rows: *mut u32) -> c_int;
+        /// two tables against each other, both only read: `out` takes the 8 words KH_CMP_* of the header names (distinct_a,
+        /// distinct_b, shared, sum_a, sum_b, shared_sum_a, shared_sum_b, sum_min); a key counts from `max(min, 1)` on
+        pub fn kh_compare(a: *mut KhCtx, b: *mut KhCtx, min_a: u64, min_b: u64, out: *mut u64) -> c_int;
+        /// `count[key] += c` in `dst` for the pairs of a set operation of `a` and `b` (op: KH_SET_*, calc: KH_CALC_*)
+        pub fn kh_combine_into(dst: *mut KhCtx, a: *mut KhCtx, b: *mut KhCtx, op: u32, calc: u32, min_a: u64, min_b: u64,
+                               n_pairs: *mut u64) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
         pub fn kh_result_text_begin(ctx: *mut KhCtx, format: u32, min_count: u64, n_records: *mut u64,
                                     n_bytes: *mut u64) -> c_int;
@@ -150,6 +156,39 @@ pub enum HipError {
 pub const ABI_VERSION: c_int = 2;
 /// `KH_PROFILE_NO_WINDOW`: an entry of [`HipKmerMap::profile`] where counting would see no window
 pub const PROFILE_NO_WINDOW: u32 = 0xFFFF_FFFF;
+
+/// The words of `kh_compare`: two tables set against each other.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct TableComparison {
+    pub distinct_a: u64,
+    pub distinct_b: u64,
+    /// keys in both sets
+    pub shared: u64,
+    /// sums of the counts over each table's set (modulo 2^64)
+    pub sum_a: u64,
+    pub sum_b: u64,
+    pub shared_sum_a: u64,
+    pub shared_sum_b: u64,
+    /// sum over the shared keys of `min(ca, cb)`
+    pub sum_min: u64,
+}
+
+impl TableComparison {
+    pub fn jaccard(&self) -> f64 { self.shared as f64 / (self.distinct_a + self.distinct_b - self.shared) as f64 }
+    pub fn containment_a(&self) -> f64 { self.shared as f64 / self.distinct_a as f64 }
+    pub fn containment_b(&self) -> f64 { self.shared as f64 / self.distinct_b as f64 }
+    pub fn bray_curtis(&self) -> f64 { 1.0 - 2.0 * self.sum_min as f64 / (self.sum_a as f64 + self.sum_b as f64) }
+}
+
+/// KH_SET_*: the set operation of `kh_combine_into`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(u32)]
+pub enum SetOp { Intersect = 1, Union = 2, Subtract = 3, CountSubtract = 4 }
+
+/// KH_CALC_*: the count of a key both tables hold (`Sum` saturates at `u64::MAX`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(u32)]
+pub enum CountRule { Min = 1, Max = 2, Sum = 3, Left = 4, Right = 5 }
 
 /// One row of [`HipKmerMap::profile_records`] (`KH_REC_*`): the reduction of a record's profile entries that are a window.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -385,6 +424,26 @@ impl HipKmerMap {
             windows: w[0], present: w[1], in_range: w[2], min: w[3], max: w[4], sum: (w[5] as u64) | ((w[6] as u64) << 32),
             first_low: if w[7] == 0xFFFF_FFFF { None } else { Some(w[7]) },
         }).collect())
+    }
+
+    /// This table (a) against `other` (b), on the device, both only read (`kh_compare`): the keys with a count of at least
+    /// `max(min_a, 1)` here and `max(min_b, 1)` there (`other` may be this table).  Jaccard, containment and Bray-Curtis are [`TableComparison`]'s methods.
+    pub fn compare(&self, other: &HipKmerMap, min_a: u64, min_b: u64) -> Result<TableComparison, HipError> {
+        let mut w = [0u64; 8];
+        check(self.ctx, unsafe { sys::kh_compare(self.ctx, other.ctx, min_a, min_b, w.as_mut_ptr()) })?;
+        Ok(TableComparison {
+            distinct_a: w[0], distinct_b: w[1], shared: w[2], sum_a: w[3], sum_b: w[4], shared_sum_a: w[5], shared_sum_b: w[6], sum_min: w[7],
+        })
+    }
+
+    /// Adds the pairs of a set operation of the tables `a` and `b` to THIS table (`kh_combine_into`: `count[key] += c`; the
+    /// table need not be empty).  `calc` is the count of a key both hold, for [`SetOp::Intersect`] and [`SetOp::Union`].
+    /// `a` and `b` are only read (the same table may be both); the borrow rules keep this table from being either.
+    /// Returns the number of pairs produced.
+    pub fn combine_into(&mut self, a: &HipKmerMap, b: &HipKmerMap, op: SetOp, calc: CountRule, min_a: u64, min_b: u64) -> Result<u64, HipError> {
+        let mut n = 0u64;
+        check(self.ctx, unsafe { sys::kh_combine_into(self.ctx, a.ctx, b.ctx, op as u32, calc as u32, min_a, min_b, &mut n) })?;
+        Ok(n)
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

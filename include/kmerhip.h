@@ -290,6 +290,55 @@ int kh_profile_records_device(kh_ctx *ctx, const uint8_t *d_bases, const uint8_t
 int kh_profile_records(kh_ctx *ctx, const uint8_t *bases, const uint8_t *qual, uint64_t n, const uint64_t *rec_start,
                        uint64_t nrec, uint32_t lo, uint32_t hi, uint32_t *rows);
 
+/* ---- two tables against each other (no reference counterpart) ------------- */
+/* What `kmc_tools simple` and Jaccard / containment screens ask of two k-mer databases, answered where both tables are: one
+ * is scanned slot by slot, the other probed per live slot -- no pair crosses the link.
+ * SETS: a key is in set A iff its count in `a` is at least max(min_a, 1); otherwise it counts as absent there, with ca = 0.
+ * Set B the same with min_b.  ca / cb below: the key's count in a / b, 0 where it is not in the set.
+ * kh_compare fills KH_CMP_WORDS words of host memory (the KH_CMP_* indices).  Derived measures are the caller's arithmetic:
+ *   Jaccard = shared / (distinct_a + distinct_b - shared);   containment of a in b = shared / distinct_a;
+ *   Bray-Curtis dissimilarity = 1 - 2 sum_min / (sum_a + sum_b).
+ * kh_combine_into adds the result pairs of a set operation to `dst` as kh_merge_pairs_device would -- count[key] += c; dst
+ * need not be empty -- and *n_pairs receives the number of pairs produced.  A pair whose computed count is 0 is never produced.
+ *   KH_SET_INTERSECT       the keys in both sets, c = calc(ca, cb)
+ *   KH_SET_UNION           the keys in either set: calc(ca, cb) for a key in both, its own count -- whatever calc -- for a key in one
+ *   KH_SET_SUBTRACT        the keys of set A that are not in set B, c = ca                        (calc is ignored)
+ *   KH_SET_COUNT_SUBTRACT  the keys of set A with ca > cb, c = ca - cb (cb = 0 for a key b lacks)  (calc is ignored)
+ * CONTRACT.  a and b are only READ, like kh_lookup: their pending pushes are counted first, each table is read in the form it
+ * is in (kh_stats.slot_bytes, distinct, kmers and grows of both stay what they were), a kh_result_text_* stream on either goes
+ * on.  The two tables may have any two sizes and forms.  a == b is allowed.  dst is entered as a writer (its text stream ends)
+ * and must be neither a nor b.  Both calls return only when they are complete: every context may be used freely afterwards.
+ * The calling thread must be the one producer of all contexts involved; the sources' streams are drained before the kernels
+ * start, which run on a's stream (kh_compare) / dst's stream (kh_combine_into).
+ * KH_ERR_BAD_ARG -- every context usable afterwards, the text in kh_last_error(dst), or kh_last_error(a) for kh_compare: a NULL
+ * context or a NULL out, dst == a or dst == b, contexts with different k or on different devices, an unknown op, an unknown
+ * calc where op uses it.
+ * SHARDS: all contexts of a call must be in the same shard state -- all full tables, or all the same (index, count) of
+ * kh_set_shard or of a finished kh_merge_across; anything else is KH_ERR_STATE.  On equal shards every word of kh_compare ADDS
+ * UP over the ranks to the full tables' value, and the union over the ranks of the kh_combine_into results is the full result. */
+#define KH_CMP_WORDS 8
+#define KH_CMP_DISTINCT_A 0    /* keys of a with count >= max(min_a, 1) */
+#define KH_CMP_DISTINCT_B 1
+#define KH_CMP_SHARED 2        /* keys in both sets */
+#define KH_CMP_SUM_A 3         /* sum of a's counts over its set (modulo 2^64) */
+#define KH_CMP_SUM_B 4
+#define KH_CMP_SHARED_SUM_A 5  /* a's counts over the shared keys */
+#define KH_CMP_SHARED_SUM_B 6
+#define KH_CMP_SUM_MIN 7       /* sum over shared keys of min(ca, cb) */
+int kh_compare(kh_ctx *a, kh_ctx *b, uint64_t min_a, uint64_t min_b, uint64_t *out /* KH_CMP_WORDS, host */);
+
+#define KH_SET_INTERSECT 1
+#define KH_SET_UNION 2
+#define KH_SET_SUBTRACT 3        /* keys of a that b does not hold; count = ca */
+#define KH_SET_COUNT_SUBTRACT 4  /* ca - cb where that is > 0 (cb = 0 for a key b lacks) */
+#define KH_CALC_MIN 1
+#define KH_CALC_MAX 2
+#define KH_CALC_SUM 3            /* saturates at 2^64 - 1 */
+#define KH_CALC_LEFT 4
+#define KH_CALC_RIGHT 5
+int kh_combine_into(kh_ctx *dst, kh_ctx *a, kh_ctx *b, uint32_t op, uint32_t calc,
+                    uint64_t min_a, uint64_t min_b, uint64_t *n_pairs /* may be NULL */);
+
 /* ---- multi-GPU merge (no reference counterpart) ----------- */
 /* Owner shard of a packed canonical k-mer among nparts shards: a fast-range of the top bits of
  * the table hash, so a shard is a contiguous range of table regions (same function on host and

@@ -7,6 +7,7 @@
 //   merge.hip     exports and merges of one context (pairs, dense, region-ordered)
 //   format.hip    kh_result_text_*: the table formatted as text on the device and streamed out in pieces
 //   profile.hip   kh_profile*: the table's count at every window start of new sequences
+//   join.hip      kh_compare / kh_combine_into: one table scanned, another probed, statistics or a third table out
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
 //
@@ -27,6 +28,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.hip.h"
@@ -321,6 +323,8 @@ struct kh_ctx {
     // kh_profile_records: the rows (KH_REC_WORDS words per record) and the record offsets, on the device for the whole call
     uint32_t *pr_rows = nullptr;  u64 pr_rows_cap = 0;  // records
     u64 *pr_rec = nullptr;        u64 pr_rec_cap = 0;   // offsets
+    // kh_compare / kh_combine_into (join.hip): the words the launching context's kernels add up -- KH_CMP_WORDS, then the pair count
+    u64 *jn_words = nullptr;
 
     bool poisoned = false;
     std::string last_error;

@@ -1,0 +1,105 @@
+// probe.hip.h -- a read-only probe of one table, in either of its forms: what profile.hip asks per window of new sequences
+// and join.hip per live slot of another table.
+#pragma once
+#include "ctx.hip.h"
+
+namespace kh {
+
+constexpr uint32_t PF_SAT = 0xFFFFFFFEu;  // the largest count an entry can say
+__device__ __forceinline__ uint32_t pf_sat(u64 count) { return count > PF_SAT ? PF_SAT : (uint32_t)count; }
+
+// The two table forms behind one interface: ref() = where a key's probe sequence starts (and whether this -- possibly shard --
+// table can hold the key at all), load() = its first slot, resolve() = the count, probing on from that slot.  free_word() is
+// what a free slot reads as: resolve() answers 0 to it, so a window that loads nothing (a key of another shard) needs no branch.
+struct PfWide {
+    TableGeom tg;
+    typedef uint4 Word;
+    struct Ref {
+        const Slot *reg;
+        u64 key;
+        uint32_t off;
+        bool mine;
+    };
+    __device__ __forceinline__ Ref ref(u64 key) const {
+        const u64 H0 = kh_table_hash(key, tg.k);
+        Ref r;
+        // (a shard holds only keys of its hash range, and places them by the bits below the owner's: the rule of ntable_lookup_kernel)
+        r.mine = !tg.shard_shift || (H0 >> (64 - tg.shard_shift)) == tg.shard_index;
+        const u64 H = H0 << tg.shard_shift;
+        r.reg = tg.table + region_of(tg, H) * REGION_SLOTS;
+        r.off = start_of(tg, H);
+        r.key = key;
+        return r;
+    }
+    __device__ static __forceinline__ Word free_word() { return make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u); }
+    __device__ static __forceinline__ Word load(const Ref &r) { return *reinterpret_cast<const uint4 *>(&r.reg[r.off]); }
+    __device__ static __forceinline__ uint32_t resolve(const Ref &r, Word w) {
+        uint32_t off = r.off;
+        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
+            const u64 sk = ((u64)w.y << 32) | w.x;
+            if (sk == r.key) return pf_sat(((u64)w.w << 32) | w.z);
+            if (sk == KH_EMPTY_KEY) return 0u;
+            off = (off + 1) & REGION_MASK;
+            w = *reinterpret_cast<const uint4 *>(&r.reg[off]);
+        }
+        return 0u;
+    }
+    // the same walk with the full count (join.hip: a table against a table)
+    __device__ static __forceinline__ u64 resolve64(const Ref &r, Word w) {
+        uint32_t off = r.off;
+        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
+            const u64 sk = ((u64)w.y << 32) | w.x;
+            if (sk == r.key) return ((u64)w.w << 32) | w.z;
+            if (sk == KH_EMPTY_KEY) return 0ull;
+            off = (off + 1) & REGION_MASK;
+            w = *reinterpret_cast<const uint4 *>(&r.reg[off]);
+        }
+        return 0ull;
+    }
+};
+
+struct PfNarrow {
+    const u64 *ntab;
+    PartGeom g;
+    typedef u64 Word;
+    struct Ref {
+        const u64 *reg;
+        uint32_t pay;
+        uint32_t off;
+        bool mine;
+    };
+    __device__ __forceinline__ Ref ref(u64 key) const {
+        const u64 H0 = kh_table_hash(key, g.k);
+        Ref r;
+        r.mine = !g.shard_shift || (H0 >> (64 - g.shard_shift)) == g.shard_index;
+        const u64 H = H0 << g.shard_shift;
+        r.pay = Pay<uint32_t>::make(key, H, g);
+        r.reg = ntab + ((u64)kh_p1_of(H, g.p1_bits) * g.b2 + kh_bucket_of_x(r.pay, g.b2)) * REGION_SLOTS;
+        r.off = narrow_start(g, r.pay);
+        return r;
+    }
+    __device__ static __forceinline__ Word free_word() { return 0ull; }
+    __device__ static __forceinline__ Word load(const Ref &r) { return r.reg[r.off]; }
+    __device__ static __forceinline__ uint32_t resolve(const Ref &r, Word w) {
+        uint32_t off = r.off;
+        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
+            if ((w >> 32) == 0) return 0u;
+            if ((uint32_t)w == r.pay) return pf_sat(w >> 32);
+            off = (off + 1) & REGION_MASK;
+            w = r.reg[off];
+        }
+        return 0u;
+    }
+    __device__ static __forceinline__ u64 resolve64(const Ref &r, Word w) {
+        uint32_t off = r.off;
+        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
+            if ((w >> 32) == 0) return 0ull;
+            if ((uint32_t)w == r.pay) return w >> 32;
+            off = (off + 1) & REGION_MASK;
+            w = r.reg[off];
+        }
+        return 0ull;
+    }
+};
+
+}  // namespace kh

@@ -9,89 +9,15 @@
 //   profile_records_kernel<QUAL, TAB>   the same first half; the tile's results are reduced per record in LDS instead of stored
 //   kh_profile_records_device / kh_profile_records   one row of KH_REC_WORDS words per record: 32 bytes cross the link, not 4 per base
 #include "ctx.hip.h"
+#include "probe.hip.h"
 
 namespace kh {
 
 constexpr uint32_t PF_NO_WINDOW = KH_PROFILE_NO_WINDOW;
-constexpr uint32_t PF_SAT = 0xFFFFFFFEu;  // the largest count an entry can say
 // a tile's 4096 results in LDS, one pad word per 32: lane l writes word j of its 16 to bank (j + l / 2 + 16 (l & 1)) mod 32 and
 // the store phase reads words 4 apart -- both without a bank conflict
 constexpr int PF_LDS = TILE + TILE / 32;
 __device__ __forceinline__ int pf_lds(int e) { return e + (e >> 5); }
-
-__device__ __forceinline__ uint32_t pf_sat(u64 count) { return count > PF_SAT ? PF_SAT : (uint32_t)count; }
-
-// The two table forms behind one interface: ref() = where a key's probe sequence starts (and whether this -- possibly shard --
-// table can hold the key at all), load() = its first slot, resolve() = the count, probing on from that slot.  free_word() is
-// what a free slot reads as: resolve() answers 0 to it, so a window that loads nothing (a key of another shard) needs no branch.
-struct PfWide {
-    TableGeom tg;
-    typedef uint4 Word;
-    struct Ref {
-        const Slot *reg;
-        u64 key;
-        uint32_t off;
-        bool mine;
-    };
-    __device__ __forceinline__ Ref ref(u64 key) const {
-        const u64 H0 = kh_table_hash(key, tg.k);
-        Ref r;
-        // (a shard holds only keys of its hash range, and places them by the bits below the owner's: the rule of ntable_lookup_kernel)
-        r.mine = !tg.shard_shift || (H0 >> (64 - tg.shard_shift)) == tg.shard_index;
-        const u64 H = H0 << tg.shard_shift;
-        r.reg = tg.table + region_of(tg, H) * REGION_SLOTS;
-        r.off = start_of(tg, H);
-        r.key = key;
-        return r;
-    }
-    __device__ static __forceinline__ Word free_word() { return make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u); }
-    __device__ static __forceinline__ Word load(const Ref &r) { return *reinterpret_cast<const uint4 *>(&r.reg[r.off]); }
-    __device__ static __forceinline__ uint32_t resolve(const Ref &r, Word w) {
-        uint32_t off = r.off;
-        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
-            const u64 sk = ((u64)w.y << 32) | w.x;
-            if (sk == r.key) return pf_sat(((u64)w.w << 32) | w.z);
-            if (sk == KH_EMPTY_KEY) return 0u;
-            off = (off + 1) & REGION_MASK;
-            w = *reinterpret_cast<const uint4 *>(&r.reg[off]);
-        }
-        return 0u;
-    }
-};
-
-struct PfNarrow {
-    const u64 *ntab;
-    PartGeom g;
-    typedef u64 Word;
-    struct Ref {
-        const u64 *reg;
-        uint32_t pay;
-        uint32_t off;
-        bool mine;
-    };
-    __device__ __forceinline__ Ref ref(u64 key) const {
-        const u64 H0 = kh_table_hash(key, g.k);
-        Ref r;
-        r.mine = !g.shard_shift || (H0 >> (64 - g.shard_shift)) == g.shard_index;
-        const u64 H = H0 << g.shard_shift;
-        r.pay = Pay<uint32_t>::make(key, H, g);
-        r.reg = ntab + ((u64)kh_p1_of(H, g.p1_bits) * g.b2 + kh_bucket_of_x(r.pay, g.b2)) * REGION_SLOTS;
-        r.off = narrow_start(g, r.pay);
-        return r;
-    }
-    __device__ static __forceinline__ Word free_word() { return 0ull; }
-    __device__ static __forceinline__ Word load(const Ref &r) { return r.reg[r.off]; }
-    __device__ static __forceinline__ uint32_t resolve(const Ref &r, Word w) {
-        uint32_t off = r.off;
-        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
-            if ((w >> 32) == 0) return 0u;
-            if ((uint32_t)w == r.pay) return pf_sat(w >> 32);
-            off = (off + 1) & REGION_MASK;
-            w = r.reg[off];
-        }
-        return 0u;
-    }
-};
 
 // out[i] for every window start i < nout of the data [vbeg, vend) (virtual positions over abase, as in count_direct_kernel):
 // the count of the window's canonical k-mer, or PF_NO_WINDOW where counting would see no window.  A lane's 16 results are the

@@ -24,6 +24,9 @@ static const char *USAGE =
     "       kmerust query <INDEX> --sequences <PATH> [-i <INPUT_FORMAT>] [-Q <MIN_QUALITY>] [-f summary|profile] [-q]\n"
     "       kmerust filter <INDEX> <PATH> [-i <INPUT_FORMAT>] [-Q <MIN_QUALITY>] [--min-count <LO>] [--max-count <HI>]\n"
     "                      [--min-kmers <N>] [--min-fraction <F>] [-v] [-q]\n"
+    "       kmerust compare <INDEX_A> <INDEX_B> [--min-count-a <N>] [--min-count-b <N>] [-f tsv|json]\n"
+    "       kmerust combine <intersect|union|subtract|count-subtract> <INDEX_A> <INDEX_B> [-c min|max|sum|left|right]\n"
+    "                       [--min-count-a <N>] [--min-count-b <N>] [-m <MIN_COUNT>] [-f <FORMAT>] [--save <SAVE>] [-q]\n"
     "\n"
     "Arguments:\n"
     "  <K>     K-mer length (1-32)\n"
@@ -50,6 +53,13 @@ static const char *USAGE =
     "      --min-kmers <N>                K-mers in range a record needs [default: 1]\n"
     "      --min-fraction <F>             ... and their share of the record's k-mers, 0-1 [default: 0]\n"
     "  -v, --invert                       Write the records the rule drops instead\n"
+    "\n"
+    "compare: two indexes set against each other on the device; one line per number: distinct_a, distinct_b, shared, sum_a, sum_b,\n"
+    "  shared_sum_a, shared_sum_b, sum_min, then jaccard, containment_a, containment_b, bray_curtis (nan where a divisor is 0).\n"
+    "combine: a set operation of two indexes, written like a count (-f, -m, --save): intersect and union give a k-mer of both\n"
+    "  indexes the count -c says [default: sum]; subtract keeps the k-mers of A that B lacks; count-subtract keeps count A - count B > 0.\n"
+    "      --min-count-a <N>              A k-mer of A below this count is taken as absent [default: 1]\n"
+    "      --min-count-b <N>              ... and of B [default: 1]\n"
     "\n"
     "  -h, --help                         Print help\n"
     "  -V, --version                      Print version\n";
@@ -262,6 +272,110 @@ static int run_filter(int argc, char **argv) {
     return 0;
 }
 
+// kmerust compare <INDEX_A> <INDEX_B> ... and kmerust combine <OP> <INDEX_A> <INDEX_B> ...: two indexes against each other (no
+// reference counterpart)
+static int run_two_indexes(int argc, char **argv, bool combine) {
+    const char *cmd = combine ? "combine" : "compare";
+    const std::string usage = combine ? "Usage: kmerust combine <OP> <INDEX_A> <INDEX_B>" : "Usage: kmerust compare <INDEX_A> <INDEX_B>";
+    std::vector<std::string> pos;
+    std::string save;
+    bool quiet = false, json = false;
+    OutputFormat fmt = combine ? OutputFormat::Fasta : OutputFormat::Tsv;
+    uint32_t calc = KH_CALC_SUM;
+    const char *calc_name = "sum";
+    uint64_t min_a = 1, min_b = 1, min_count = 1;
+    auto value_of = [&](int &i, const std::string &arg, const char *name) -> std::string {
+        const size_t eq = arg.find('=');
+        if (arg.rfind("--", 0) == 0 && eq != std::string::npos) return arg.substr(eq + 1);
+        if (arg.rfind("--", 0) != 0 && arg.size() > 2) return arg.substr(2);  // -fVALUE
+        if (i + 1 >= argc) usage_error(std::string("a value is required for '") + name + "' but none was supplied");
+        return argv[++i];
+    };
+    for (int i = 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        const std::string key = a.rfind("--", 0) == 0 ? a.substr(0, a.find('=')) : a.substr(0, 2);
+        if (a == "-q" || a == "--quiet") {
+            quiet = true;
+        } else if (key == "--min-count-a") {
+            min_a = parse_u64(value_of(i, a, "--min-count-a <N>"), "--min-count-a <N>", UINT64_MAX);
+        } else if (key == "--min-count-b") {
+            min_b = parse_u64(value_of(i, a, "--min-count-b <N>"), "--min-count-b <N>", UINT64_MAX);
+        } else if (key == "-f" || key == "--format") {
+            const std::string v = value_of(i, a, "--format <FORMAT>");
+            if (!combine) {
+                if (v == "tsv") json = false;
+                else if (v == "json") json = true;
+                else usage_error("invalid value '" + v + "' for '--format <FORMAT>'\n  [possible values: tsv, json]");
+            } else if (v == "fasta") fmt = OutputFormat::Fasta;
+            else if (v == "tsv") fmt = OutputFormat::Tsv;
+            else if (v == "json") fmt = OutputFormat::Json;
+            else if (v == "histogram") fmt = OutputFormat::Histogram;
+            else usage_error("invalid value '" + v + "' for '--format <FORMAT>'\n  [possible values: fasta, tsv, json, histogram]");
+        } else if (combine && (key == "-c" || key == "--calc")) {
+            const std::string v = value_of(i, a, "--calc <CALC>");
+            if (v == "min") calc = KH_CALC_MIN, calc_name = "min";
+            else if (v == "max") calc = KH_CALC_MAX, calc_name = "max";
+            else if (v == "sum") calc = KH_CALC_SUM, calc_name = "sum";
+            else if (v == "left") calc = KH_CALC_LEFT, calc_name = "left";
+            else if (v == "right") calc = KH_CALC_RIGHT, calc_name = "right";
+            else usage_error("invalid value '" + v + "' for '--calc <CALC>'\n  [possible values: min, max, sum, left, right]");
+        } else if (combine && (key == "-m" || key == "--min-count")) {
+            min_count = parse_u64(value_of(i, a, "--min-count <MIN_COUNT>"), "--min-count <MIN_COUNT>", UINT64_MAX);
+        } else if (combine && key == "--save") {
+            save = value_of(i, a, "--save <SAVE>");
+        } else if (a.size() > 1 && a[0] == '-' && a != "-") {
+            usage_error("unexpected argument '" + a + "' found");
+        } else if (pos.size() < (combine ? 3u : 2u)) {
+            pos.push_back(a);
+        } else {
+            usage_error("unexpected argument '" + a + "' found");
+        }
+    }
+    uint32_t op = 0;
+    if (combine && !pos.empty()) {
+        const std::string &v = pos[0];
+        if (v == "intersect") op = KH_SET_INTERSECT;
+        else if (v == "union") op = KH_SET_UNION;
+        else if (v == "subtract") op = KH_SET_SUBTRACT;
+        else if (v == "count-subtract") op = KH_SET_COUNT_SUBTRACT;
+        else usage_error("invalid value '" + v + "' for '<OP>'\n  [possible values: intersect, union, subtract, count-subtract]");
+    }
+    static const char *const names[3] = {"<OP>", "<INDEX_A>", "<INDEX_B>"};
+    const size_t need = combine ? 3 : 2;
+    if (pos.size() < need) {
+        std::string msg = "the following required arguments were not provided:";
+        for (size_t j = pos.size(); j < need; ++j) msg += std::string("\n  ") + names[j + (combine ? 0 : 1)];
+        usage_error(msg + "\n\n" + usage);
+    }
+    const std::string &ia = pos[need - 2], &ib = pos[need - 1];
+    if (!quiet) {
+        if (combine) fprintf(stderr, "operation: %s\n", pos[0].c_str());
+        fprintf(stderr, "index-a: %s\nindex-b: %s\n", ia.c_str(), ib.c_str());
+        if (combine && (op == KH_SET_INTERSECT || op == KH_SET_UNION)) fprintf(stderr, "calc: %s\n", calc_name);
+        if (min_a > 1) fprintf(stderr, "min-count-a: %llu\n", (unsigned long long)min_a);
+        if (min_b > 1) fprintf(stderr, "min-count-b: %llu\n", (unsigned long long)min_b);
+        if (combine && min_count > 1) fprintf(stderr, "min-count: %llu\n", (unsigned long long)min_count);
+        if (!save.empty()) fprintf(stderr, "save-index: %s\n", save.c_str());
+        fprintf(stderr, "\n");
+    }
+#if !defined(__SANITIZE_ADDRESS__) && !defined(KMERUST_UNDER_ASAN) && !defined(KMERUST_ALWAYS_CLEAN_EXIT)  // (as cli_main)
+    leak_at_exit() = !getenv("KMERUST_CLEAN_EXIT");
+#endif
+    try {
+        if (combine) {
+            uint64_t n = 0;
+            combine_indexes(op, calc, ia, ib, min_a, min_b, min_count, fmt, save, stdout, &n);
+            if (!quiet && !save.empty()) fprintf(stderr, "saved: %s (%llu k-mers)\n", save.c_str(), (unsigned long long)n);
+        } else {
+            compare_indexes(ia, ib, min_a, min_b, json, stdout);
+        }
+    } catch (const Error &e) {
+        fprintf(stderr, "Application error:\n %s: %s\n", cmd, e.what());
+        return 1;
+    }
+    return 0;
+}
+
 static int run_query(int argc, char **argv) {
     for (int i = 2; i < argc; ++i)
         if (!strncmp(argv[i], "--sequences", 11) && (argv[i][11] == 0 || argv[i][11] == '=')) return run_query_sequences(argc, argv);
@@ -328,6 +442,8 @@ static int run_parse_dump(int argc, char **argv) {
 int cli_main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "query")) return run_query(argc, argv);  // src/main.rs:39-47
     if (argc > 1 && !strcmp(argv[1], "filter")) return run_filter(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "compare")) return run_two_indexes(argc, argv, false);
+    if (argc > 1 && !strcmp(argv[1], "combine")) return run_two_indexes(argc, argv, true);
     if (argc > 1 && !strcmp(argv[1], "__parse")) return run_parse_dump(argc, argv);
 
     std::string k_arg, path = "-", save;

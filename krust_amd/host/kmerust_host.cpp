@@ -26,6 +26,9 @@
 #pragma weak kh_profile
 #pragma weak kh_merge_pairs
 #pragma weak kh_profile_records
+// ... and of `compare` / `combine`
+#pragma weak kh_compare
+#pragma weak kh_combine_into
 
 namespace kmerust {
 
@@ -1140,8 +1143,8 @@ namespace {
 struct IndexTable {
     kh_ctx *c = nullptr;
     uint32_t k = 0;
-    IndexTable(const std::string &index_path, int min_quality) {
-        const PackedCounts idx = load_index(index_path);
+    IndexTable(const std::string &index_path, int min_quality) : IndexTable(load_index(index_path), min_quality) {}
+    IndexTable(const PackedCounts &idx, int min_quality) {
         kh_config cfg;
         memset(&cfg, 0, sizeof(cfg));
         cfg.struct_size = sizeof(cfg);
@@ -1194,6 +1197,76 @@ void query_sequences(const std::string &index_path, const std::string &path, Seq
         ordinal += write_profile_lines(out, b.bases.data(), prof.data(), b.bases.size(), ctx.k, out_fmt, ordinal);
     });
     if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+}
+
+// =============================================================================================
+// two indexes against each other
+// =============================================================================================
+void write_compare(FILE *out, const uint64_t *words, bool json) {
+    static const char *const names[KH_CMP_WORDS] = {"distinct_a", "distinct_b", "shared", "sum_a", "sum_b", "shared_sum_a", "shared_sum_b", "sum_min"};
+    const CompareMeasures m = compare_measures(words);
+    const std::pair<const char *, double> ms[4] = {{"jaccard", m.jaccard}, {"containment_a", m.containment_a}, {"containment_b", m.containment_b},
+                                                   {"bray_curtis", m.bray_curtis}};
+    if (json) {
+        fputc('{', out);
+        for (int i = 0; i < KH_CMP_WORDS; ++i) fprintf(out, "\"%s\": %llu, ", names[i], (unsigned long long)words[i]);
+        for (int i = 0; i < 4; ++i) fprintf(out, "\"%s\": %s%s", ms[i].first, std::isnan(ms[i].second) ? "NaN" : format_measure(ms[i].second).c_str(), i < 3 ? ", " : "");
+        fputs("}\n", out);
+    } else {
+        for (int i = 0; i < KH_CMP_WORDS; ++i) fprintf(out, "%s\t%llu\n", names[i], (unsigned long long)words[i]);
+        for (int i = 0; i < 4; ++i) fprintf(out, "%s\t%s\n", ms[i].first, format_measure(ms[i].second).c_str());
+    }
+}
+
+namespace {
+// both indexes, and the refusal of two different k before anything touches the device
+void load_two(const std::string &index_a, const std::string &index_b, PackedCounts &a, PackedCounts &b) {
+    a = load_index(index_a);
+    b = load_index(index_b);
+    if (a.k != b.k)
+        throw Error("k-mer length mismatch: " + index_a + " has k=" + std::to_string(a.k) + ", " + index_b + " has k=" + std::to_string(b.k));
+}
+}  // namespace
+
+void compare_indexes(const std::string &index_a, const std::string &index_b, uint64_t min_a, uint64_t min_b, bool json, FILE *out) {
+    if (!kh_compare || !kh_merge_pairs)
+        throw Error("compare needs a kmerhip library with kh_compare and kh_merge_pairs; the one this program was built against has neither");
+    PackedCounts pa, pb;
+    load_two(index_a, index_b, pa, pb);
+    IndexTable a(pa, -1), b(pb, -1);
+    uint64_t words[KH_CMP_WORDS];
+    Session::check_on(a.c, kh_compare(a.c, b.c, min_a, min_b, words), "kh_compare");
+    write_compare(out, words, json);
+    if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+}
+
+void combine_indexes(uint32_t op, uint32_t calc, const std::string &index_a, const std::string &index_b, uint64_t min_a, uint64_t min_b,
+                     uint64_t min_count, OutputFormat fmt, const std::string &save, FILE *out, uint64_t *n_pairs) {
+    if (!kh_combine_into || !kh_merge_pairs)
+        throw Error("combine needs a kmerhip library with kh_combine_into and kh_merge_pairs; the one this program was built against has neither");
+    PackedCounts pa, pb;
+    load_two(index_a, index_b, pa, pb);
+    IndexTable a(pa, -1), b(pb, -1);
+    const uint64_t na = pa.keys.size(), nb = pb.keys.size();
+    KmerCounter kc;
+    kc.k(pa.k).capacity_hint(op == KH_SET_UNION ? na + nb : op == KH_SET_INTERSECT ? std::min(na, nb) : na);
+    pa = PackedCounts();  // (the host copies are no longer needed)
+    pb = PackedCounts();
+    Session s(kc, false);
+    uint64_t n = 0;
+    s.check(kh_combine_into(s.ctx, a.c, b.c, op, calc, min_a, min_b, &n), "kh_combine_into");
+    if (n_pairs) *n_pairs = n;
+    if (!save.empty()) {  // as `kmerust --save`: the index holds ALL pairs, the output honours min_count
+        const PackedCounts all = s.result(1);
+        save_index(all, save);
+        if (fmt == OutputFormat::Histogram || !s.device_text_ok(fmt)) {
+            write_counts(out, all, fmt, min_count);
+            return;
+        }
+    }
+    if (fmt == OutputFormat::Histogram) write_histogram(out, s.histogram(min_count));
+    else if (s.device_text_ok(fmt)) s.write_text(out, fmt, min_count);
+    else write_counts(out, s.result(min_count), fmt, 1);
 }
 
 // =============================================================================================

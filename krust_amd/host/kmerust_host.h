@@ -11,6 +11,7 @@
 //   CLI                                            src/cli.rs:33-144, src/main.rs:34-299
 // Counting itself always goes through kh_* (the HIP path); there is no CPU counting here.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -174,6 +175,43 @@ void append_record(std::string &dst, const std::string &header, const uint8_t *s
 // order, to out.  min_quality masks on the device (FASTQ files only, as in counting).  Throws Error.
 void filter_sequences(const std::string &index_path, const std::string &path, SequenceFormat fmt, int min_quality, const FilterRule &rule,
                       FILE *out, uint64_t *records, uint64_t *kept, size_t batch_bytes = 0);
+
+// ---- two indexes against each other (`kmerust compare` / `kmerust combine`; no reference counterpart) -------------------------------
+// The measures `kmerust compare` derives from the KH_CMP_WORDS words of kh_compare: jaccard = shared / (distinct_a + distinct_b -
+// shared), containment_a = shared / distinct_a, containment_b = shared / distinct_b, bray_curtis = 1 - 2 sum_min / (sum_a + sum_b).
+// A division by zero gives NaN.  Pure: no device, no library call.
+struct CompareMeasures {
+    double jaccard, containment_a, containment_b, bray_curtis;
+};
+inline CompareMeasures compare_measures(const uint64_t *words) {
+    const double nan = std::nan("");
+    const double da = (double)words[KH_CMP_DISTINCT_A], db = (double)words[KH_CMP_DISTINCT_B], sh = (double)words[KH_CMP_SHARED];
+    const double sums = (double)words[KH_CMP_SUM_A] + (double)words[KH_CMP_SUM_B];
+    CompareMeasures m;
+    m.jaccard = da + db - sh > 0 ? sh / (da + db - sh) : nan;
+    m.containment_a = da > 0 ? sh / da : nan;
+    m.containment_b = db > 0 ? sh / db : nan;
+    m.bray_curtis = sums > 0 ? 1.0 - 2.0 * (double)words[KH_CMP_SUM_MIN] / sums : nan;
+    return m;
+}
+// "%.6f", or "nan" (never "-nan")
+inline std::string format_measure(double v) {
+    if (std::isnan(v)) return "nan";
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%.6f", v);
+    return buf;
+}
+// The eight words by name, then the four measures: tsv = one "{name}\t{value}" line each; json = one object on one line (a
+// measure that is NaN is written as NaN).
+void write_compare(FILE *out, const uint64_t *words, bool json);
+// Both indexes into device tables (as `query --sequences` loads one), kh_compare, write_compare.  Indexes with different k: an Error
+// that names both, before any device call.  Throws Error.
+void compare_indexes(const std::string &index_a, const std::string &index_b, uint64_t min_a, uint64_t min_b, bool json, FILE *out);
+// Both indexes into device tables, a third context of the same k, kh_combine_into(op, calc: KH_SET_* / KH_CALC_*), and that context
+// through the writers of the counting command: `save` (unless empty) takes ALL result pairs as an index, `out` the records with
+// count >= min_count in format `fmt` (the device text stream where the format has one).  *n_pairs (optional): pairs produced.
+void combine_indexes(uint32_t op, uint32_t calc, const std::string &index_a, const std::string &index_b, uint64_t min_a, uint64_t min_b,
+                     uint64_t min_count, OutputFormat fmt, const std::string &save, FILE *out, uint64_t *n_pairs = nullptr);
 
 // ---- KMIX index (src/index.rs) -----------------------------------------------------------------
 uint32_t crc32_ieee(const uint8_t *data, size_t n, uint32_t crc = 0);  // src/index.rs:404-431

@@ -30,6 +30,14 @@ PROFILE_NO_WINDOW = 0xFFFFFFFF  # KH_PROFILE_NO_WINDOW: an entry of kh_profile* 
 # KH_REC_*: the words of a row of kh_profile_records*
 REC_WORDS = 8
 REC_WINDOWS, REC_PRESENT, REC_IN_RANGE, REC_MIN, REC_MAX, REC_SUM_LO, REC_SUM_HI, REC_FIRST_LOW = range(8)
+# KH_CMP_*: the words of kh_compare; KH_SET_* / KH_CALC_*: the set operations and count rules of kh_combine_into
+CMP_WORDS = 8
+CMP_DISTINCT_A, CMP_DISTINCT_B, CMP_SHARED, CMP_SUM_A, CMP_SUM_B, CMP_SHARED_SUM_A, CMP_SHARED_SUM_B, CMP_SUM_MIN = range(8)
+CMP_NAMES = ("distinct_a", "distinct_b", "shared", "sum_a", "sum_b", "shared_sum_a", "shared_sum_b", "sum_min")
+SET_INTERSECT, SET_UNION, SET_SUBTRACT, SET_COUNT_SUBTRACT = 1, 2, 3, 4
+CALC_MIN, CALC_MAX, CALC_SUM, CALC_LEFT, CALC_RIGHT = 1, 2, 3, 4, 5
+_SET_OPS = {"intersect": SET_INTERSECT, "union": SET_UNION, "subtract": SET_SUBTRACT, "count-subtract": SET_COUNT_SUBTRACT}
+_CALCS = {"min": CALC_MIN, "max": CALC_MAX, "sum": CALC_SUM, "left": CALC_LEFT, "right": CALC_RIGHT}
 
 
 class KhConfig(C.Structure):
@@ -89,6 +97,8 @@ SYMBOLS = {
     "kh_profile": (C.c_int, [_P, _P, _P, _U64, _P]),
     "kh_profile_records_device": (C.c_int, [_P, _P, _P, _U64, _P, _U64, C.c_uint32, C.c_uint32, _P]),
     "kh_profile_records": (C.c_int, [_P, _P, _P, _U64, _P, _U64, C.c_uint32, C.c_uint32, _P]),
+    "kh_compare": (C.c_int, [_P, _P, _U64, _U64, _P]),
+    "kh_combine_into": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _U64, _U64, C.POINTER(_U64)]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
     "kh_set_shard": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "kh_set_region_window": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -429,6 +439,25 @@ class DeviceCounter:
         ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
         self._check(lib().kh_profile_records_device(self._h, ptr(d_bases), ptr(d_qual), int(n), ptr(d_rec_start), int(nrec), int(lo),
                                                     int(hi), ptr(d_rows)))
+
+    # -- two tables against each other ---------------------------------------
+    def compare(self, other, min_a=1, min_b=1):
+        """kh_compare of this table (a) and `other` (b), both only read: a dict of the eight words -- distinct_a, distinct_b,
+        shared, sum_a, sum_b, shared_sum_a, shared_sum_b, sum_min -- over the keys with a count >= max(min_a, 1) here and
+        >= max(min_b, 1) there.  Jaccard = shared / (distinct_a + distinct_b - shared), containment = shared / distinct_a,
+        Bray-Curtis = 1 - 2 sum_min / (sum_a + sum_b)."""
+        out = np.zeros(CMP_WORDS, dtype=np.uint64)
+        self._check(lib().kh_compare(self._h, other._h, int(min_a), int(min_b), out.ctypes.data))
+        return dict(zip(CMP_NAMES, (int(x) for x in out)))
+
+    def combine_into(self, a, b, op, calc=CALC_SUM, min_a=1, min_b=1):
+        """kh_combine_into: adds the pairs of the set operation `op` ("intersect" | "union" | "subtract" | "count-subtract" or
+        SET_*) of the tables a and b to THIS table (count[key] += c); calc ("min" | "max" | "sum" | "left" | "right" or CALC_*)
+        is the count of a key both hold.  a and b are only read; this table must be neither.  Returns the number of pairs."""
+        n = _U64(0)
+        self._check(lib().kh_combine_into(self._h, a._h, b._h, int(_SET_OPS.get(op, op)), int(_CALCS.get(calc, calc)), int(min_a),
+                                          int(min_b), C.byref(n)))
+        return int(n.value)
 
     # -- multi-GPU merge ---------------------------------------------------
     def comm_init(self, nranks, rank, unique_id):
