@@ -115,6 +115,10 @@ pub mod sys {
         pub fn kh_combine_into(dst: *mut KhCtx, a: *mut KhCtx, b: *mut KhCtx, op: u32, calc: u32, min_a: u64, min_b: u64,
                                n_pairs: *mut u64) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
+        pub fn kh_result_sorted(ctx: *mut KhCtx, keys: *mut u64, counts: *mut u64, cap: u64,
+                                min_count: u64, n: *mut u64) -> c_int;
+        pub fn kh_result_sorted_device(ctx: *mut KhCtx, d_keys: *mut u64, d_counts: *mut u64, cap: u64,
+                                       min_count: u64, n: *mut u64) -> c_int;
         pub fn kh_result_text_begin(ctx: *mut KhCtx, format: u32, min_count: u64, n_records: *mut u64,
                                     n_bytes: *mut u64) -> c_int;
         /// whole records, at most `cap` bytes; `*n == 0`: the stream has ended; -8 (KH_ERR_RANGE): cap < the next record
@@ -207,6 +211,9 @@ pub struct RecordAbundance {
     /// offset from the record start of the first window whose count is `< lo`
     pub first_low: Option<u32>,
 }
+
+/// `KH_OUT_SORTED`: ORed into the format of `kh_result_text_begin`, the records come in ascending key order.
+pub const KH_OUT_SORTED: u32 = 0x100;
 
 /// The record formats of `kh_result_text_begin` (`KH_OUT_*`): the reference's `OutputFormat` without the histogram.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -461,13 +468,40 @@ impl HipKmerMap {
         Ok(keys.into_iter().zip(counts).take(got as usize).collect())
     }
 
+    /// The pairs with count >= `min_count`, ASCENDING by packed key -- the k-mer strings in lexicographic order --, sorted on
+    /// the device (`kh_result_sorted`).  The same input gives the same vectors whatever the table's size or form.
+    pub fn sorted_pairs(&mut self, min_count: u64) -> Result<(Vec<u64>, Vec<u64>), HipError> {
+        check(self.ctx, unsafe { sys::kh_finish(self.ctx, std::ptr::null_mut()) })?;
+        let mut n = 0u64;
+        check(self.ctx, unsafe { sys::kh_result_size(self.ctx, min_count, &mut n) })?;
+        let mut keys = vec![0u64; n as usize];
+        let mut counts = vec![0u64; n as usize];
+        let mut got = 0u64;
+        check(self.ctx, unsafe {
+            sys::kh_result_sorted(self.ctx, keys.as_mut_ptr(), counts.as_mut_ptr(), n, min_count, &mut got)
+        })?;
+        keys.truncate(got as usize);
+        counts.truncate(got as usize);
+        Ok((keys, counts))
+    }
+
+    /// [`write_text`](Self::write_text) with the records in ascending key order (`KH_OUT_SORTED`): the same table content
+    /// gives the same bytes on every run and for every table geometry.
+    pub fn write_text_sorted<W: std::io::Write>(&mut self, format: TextFormat, min_count: u64, w: &mut W) -> Result<(u64, u64), HipError> {
+        self.write_text_as(format as u32 | KH_OUT_SORTED, min_count, w)
+    }
+
     /// `output_counts` (`src/run.rs:441-486`) for the fasta / tsv / json formats: the records are unpacked, their counts
     /// printed and the JSON document framed ON THE DEVICE; `w` receives the text in pieces of whole records, in table
     /// order.  Returns (records, bytes) written.  The table stays as it is (`&mut self`: the stream is state of the context).
     pub fn write_text<W: std::io::Write>(&mut self, format: TextFormat, min_count: u64, w: &mut W) -> Result<(u64, u64), HipError> {
+        self.write_text_as(format as u32, min_count, w)
+    }
+
+    fn write_text_as<W: std::io::Write>(&mut self, format: u32, min_count: u64, w: &mut W) -> Result<(u64, u64), HipError> {
         check(self.ctx, unsafe { sys::kh_finish(self.ctx, std::ptr::null_mut()) })?;
         let (mut n_records, mut n_bytes) = (0u64, 0u64);
-        check(self.ctx, unsafe { sys::kh_result_text_begin(self.ctx, format as u32, min_count, &mut n_records, &mut n_bytes) })?;
+        check(self.ctx, unsafe { sys::kh_result_text_begin(self.ctx, format, min_count, &mut n_records, &mut n_bytes) })?;
         let mut piece = vec![0u8; (n_bytes.min(8 << 20) as usize).max(128)];
         let mut written = 0u64;
         loop {

@@ -198,6 +198,21 @@ int kh_result_copy(kh_ctx *ctx, uint64_t *keys, uint64_t *counts, uint64_t cap,
  *     the context stays usable.  (One pass over the table: the size is known only when the pairs are out.) */
 int kh_result_copy_device(kh_ctx *ctx, uint64_t *d_keys, uint64_t *d_counts, uint64_t cap,
                           uint64_t min_count, uint64_t *n);
+/* The same pairs in ASCENDING order of the packed key -- which is lexicographic order of the k-mer strings (A < C < G < T, first
+ * base most significant) -- sorted on the device: an LSD radix sort over the 2k significant key bits.  The order does not
+ * depend on the table's size, geometry or form (16-byte table / 8-byte image: both are read as they are, kh_stats.slot_bytes,
+ * distinct, kmers and grows stay what they were), so two runs over the same input give the same arrays.  A shard table
+ * (kh_set_shard, or after kh_merge_across) gives its own keys in ascending order.
+ *   - BOTH forms take the size first: a cap smaller than kh_result_size(min_count) is KH_ERR_RANGE with *n = 0 and NOTHING
+ *     written to either array (kh_result_copy's rule, not kh_result_copy_device's); the context stays usable.
+ *   - min_count = 0 selects what 1 selects.  cap = 0 takes NULL arrays.
+ *   - Scratch (a second pair of arrays and the digit histograms) comes from the idle partition buffers, else from the device;
+ *     KH_ERR_OOM when there is none -- the context stays usable and nothing stays allocated.
+ *   - Like kh_result_copy they end a running kh_result_text_* stream (they take the same scratch memory). */
+int kh_result_sorted_device(kh_ctx *ctx, uint64_t *d_keys, uint64_t *d_counts, uint64_t cap,
+                            uint64_t min_count, uint64_t *n);
+int kh_result_sorted(kh_ctx *ctx, uint64_t *keys, uint64_t *counts, uint64_t cap,
+                     uint64_t min_count, uint64_t *n);
 /* The same result as TEXT, formatted on the device: replaces output_counts (src/run.rs:441-486) -- unpacking, the decimal
  * counts and the framing happen in HBM, and only text crosses the link.  Three formats, byte for byte the reference's:
  *   KH_OUT_FASTA  >{count}\n{kmer}\n          KH_OUT_TSV  {kmer}\t{count}\n
@@ -206,14 +221,14 @@ int kh_result_copy_device(kh_ctx *ctx, uint64_t *d_keys, uint64_t *d_counts, uin
  * A pull interface, because the text can be larger than any one buffer: kh_result_text_begin sizes the stream
  * (*n_records, *n_bytes: its totals, either may be NULL), every kh_result_text_next* hands out the next piece --
  * WHOLE records, at most cap bytes -- and *n = 0 with KH_OK says that the stream has ended.
- *   - Records come in table-slot order; the same table gives the same bytes on every run, and the concatenation of the
+ *   - Records come in table-slot order (ascending key order with KH_OUT_SORTED); the same table gives the same bytes on every run, and the concatenation of the
  *     pieces is the same document for EVERY sequence of cap values.
  *   - JSON: the opening "[\n" belongs to the first record; the closing "\n]\n" follows the last record in the same piece
  *     when it fits there, else it is a piece of its own.
  *   - A cap smaller than the next record: KH_ERR_RANGE, nothing is consumed (call again with more room).
  *   - next without begin: KH_ERR_STATE.  So is next after any call that entered the context for something else than
- *     reading -- every kh_push*, kh_reset, kh_merge_*, kh_set_shard, the exports, kh_result_copy (which takes the same
- *     scratch memory): begin again.  kh_result_size, kh_lookup, kh_histogram and kh_finish may be interleaved.
+ *     reading -- every kh_push*, kh_reset, kh_merge_*, kh_set_shard, the exports, kh_result_copy / kh_result_sorted* (which take the
+ *     same scratch memory): begin again.  kh_result_size, kh_lookup, kh_histogram and kh_finish may be interleaved.
  *   - begin on a running stream restarts it.  Shard tables (kh_set_shard / kh_merge_across) stream like full ones.
  *   - kh_result_text_next takes pageable memory, or -- faster: no bounce -- memory of kh_host_alloc / kh_host_register;
  *     the next range of the table is formatted while the current one travels.  kh_result_text_next_device writes
@@ -224,6 +239,13 @@ int kh_result_copy_device(kh_ctx *ctx, uint64_t *d_keys, uint64_t *d_counts, uin
 #define KH_OUT_FASTA 1
 #define KH_OUT_TSV 2
 #define KH_OUT_JSON 3
+/* ORed into `format` of kh_result_text_begin: the records come in ASCENDING KEY order (the k-mer strings in lexicographic order)
+ * instead of table-slot order.  begin sorts the result on the device (kh_result_sorted_device) into memory the stream owns --
+ * 16 bytes per record, released by kh_destroy; KH_ERR_OOM when it cannot be had -- and everything else of the stream's contract
+ * is unchanged: totals, whole records per piece, the same document for every sequence of cap values, JSON framing, the
+ * KH_ERR_RANGE / KH_ERR_STATE rules, interleaved readers, next_device.  On top of it the same table CONTENT gives the same
+ * bytes whatever the table's size, geometry or form.  Any other bit beside the three formats: KH_ERR_BAD_ARG. */
+#define KH_OUT_SORTED 0x100u
 int kh_result_text_begin(kh_ctx *ctx, uint32_t format, uint64_t min_count, uint64_t *n_records, uint64_t *n_bytes);
 int kh_result_text_next(kh_ctx *ctx, uint8_t *buf, uint64_t cap, uint64_t *n);
 int kh_result_text_next_device(kh_ctx *ctx, uint8_t *d_buf, uint64_t cap, uint64_t *n);

@@ -8,6 +8,7 @@
 //   format.hip    kh_result_text_*: the table formatted as text on the device and streamed out in pieces
 //   profile.hip   kh_profile*: the table's count at every window start of new sequences
 //   join.hip      kh_compare / kh_combine_into: one table scanned, another probed, statistics or a third table out
+//   sort.hip      kh_result_sorted*: the result pairs in ascending key order (a device radix sort; format.hip streams it as text)
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
 //
@@ -306,12 +307,16 @@ struct kh_ctx {
             hipEvent_t done = nullptr;      // its formatting kernel (on `stream`)
         } ch[2];
         int cur = 0;                       // the chunk being handed out
+        bool sorted = false;               // KH_OUT_SORTED: the tiles are over ts_skey / ts_scnt (sorted_n pairs, ascending), not over the table
+        u64 sorted_n = 0;
     } ts;
     uint8_t *ts_own[2] = {nullptr, nullptr};  u64 ts_own_cap[2] = {0, 0};  // chunks of the stream's own (no partition buffers to use)
     uint32_t *ts_trec = nullptr;  u64 ts_trec_cap = 0;   // per tile: records
     uint32_t *ts_tbyt = nullptr;  u64 ts_tbyt_cap = 0;   // per tile: bytes
     u64 *ts_roff = nullptr;       u64 ts_roff_cap = 0;   // exclusive scans of the two
     u64 *ts_boff = nullptr;       u64 ts_boff_cap = 0;
+    u64 *ts_skey = nullptr;       u64 ts_skey_cap = 0;   // a sorted stream's pairs: the stream's own memory, never where its chunks live
+    u64 *ts_scnt = nullptr;       u64 ts_scnt_cap = 0;
 
     // ---- kh_profile: the chunks of the host form (profile.hip) ----
     // two device buffers [bases | qualities | profile] for pf_chunk window starts each, their pinned twins (the bounce of pageable
@@ -384,6 +389,9 @@ int end_borrow(kh_ctx *c);            // the partition buffers are about to be w
 void drop_table(kh_ctx *c);           // the 16-byte table is no longer needed: freed, unless it was borrowed
 int device_scan(kh_ctx *c, const uint32_t *in, u64 n, u64 *out);
 int zero_cursors(kh_ctx *c);
+// the live pairs with count >= min_count into device arrays of capacity cap, in no particular order (what kh_result_copy_device
+// does once it has entered the context): *n = pairs written; KH_ERR_RANGE when the table holds more than cap
+int compact_pairs(kh_ctx *c, u64 *d_keys, u64 *d_counts, u64 cap, u64 min_count, u64 *n);
 int read_cursor(kh_ctx *c, u64 *cursor, u64 *big);
 int head_count_bits(const kh_ctx *c, u64 regions);
 extern bool g_pow2_tables;
@@ -414,6 +422,21 @@ int merge_regions(kh_ctx *c, int fmt, uint32_t nsenders, uint64_t sender_regions
 void comm_release(kh_ctx *c);
 // ---- format.hip
 void text_release(kh_ctx *c);  // kh_destroy: the text stream's buffers and events
+// ---- sort.hip
+// Device memory for the length of one call: the idle partition buffers when nothing is borrowed, else borrow(), else hipMalloc.
+// take() returns nullptr when there is none (the context stays usable); the destructor gives everything back.
+struct SortScratch {
+    kh_ctx *c;
+    u64 loan0, loan1;
+    u64 used[2] = {0, 0};
+    std::vector<void *> owned;
+    explicit SortScratch(kh_ctx *ctx);
+    ~SortScratch();
+    SortScratch(const SortScratch &) = delete;
+    SortScratch &operator=(const SortScratch &) = delete;
+    void *take(u64 bytes);
+};
+int sorted_into(kh_ctx *c, u64 *out_keys, u64 *out_counts, u64 n, u64 min_count, SortScratch &sc);
 // ---- profile.hip
 void profile_release(kh_ctx *c);  // kh_destroy: the chunk buffers and events of kh_profile, the rows of kh_profile_records
 

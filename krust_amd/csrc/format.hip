@@ -4,6 +4,8 @@
 // host and a formatting loop there, the device writes the records (format.hip.h) and only text crosses the link.
 //   begin   fmt_size_kernel: records and bytes of every tile of FMT_TILE slots; two exclusive scans (device_scan): a
 //           deterministic byte offset per tile -- no atomic cursor, the text is in table-slot order
+//           KH_OUT_SORTED: the tiles are over the sorted pairs (sorted_into, sort.hip), which the stream holds in memory of its own;
+//           a third loader (FmtSorted) reads them, everything behind the loader is the same
 //   next    a range of whole tiles -> fmt_tiles_kernel -> one of two device chunks; the chunk's text is handed out
 //           record-aligned.  Chunk i + 1 is formatted on the compute stream while chunk i travels on the copy stream.
 #include "ctx.hip.h"
@@ -22,19 +24,22 @@ void text_release(kh_ctx *c) {
         if (c->ts_own[i]) (void)hipFree(c->ts_own[i]);
         c->ts_own[i] = nullptr;
     }
-    void *bufs[] = {c->ts_trec, c->ts_tbyt, c->ts_roff, c->ts_boff};
+    void *bufs[] = {c->ts_trec, c->ts_tbyt, c->ts_roff, c->ts_boff, c->ts_skey, c->ts_scnt};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     c->ts_trec = c->ts_tbyt = nullptr;
     c->ts_roff = c->ts_boff = nullptr;
+    c->ts_skey = c->ts_scnt = nullptr;
 }
 
 namespace {
 
+// f(loader, slots): what the tiles are over -- the sorted pairs of the stream, or the table in the form it is in
 template <typename F>
-void with_loader(const kh_ctx *c, F f) {
-    if (c->narrow) f(kh::FmtNarrow{(const u64 *)c->ntab, c->narrow_g});
-    else f(kh::FmtWide{c->table});
+void with_loader(const kh_ctx *c, bool sorted, u64 sorted_n, F f) {
+    if (sorted) f(kh::FmtSorted{(const u64 *)c->ts_skey, (const u64 *)c->ts_scnt}, sorted_n);
+    else if (c->narrow) f(kh::FmtNarrow{(const u64 *)c->ntab, c->narrow_g}, c->cap);
+    else f(kh::FmtWide{c->table}, c->cap);
 }
 
 // The device memory of chunk i: half of the idle partition buffers (as kh_result_copy takes them: nothing counts while a stream
@@ -79,8 +84,8 @@ int format_range(kh_ctx *c, uint8_t *dst, u64 limit, u64 *len) {
     for (u64 s = a; s < b;) {  // (a grid dimension holds 2^31 - 1 workgroups)
         const u64 n = std::min<u64>(b - s, 1ull << 30);
         uint8_t *const d = dst + (ts.toff[s] - b0);
-        with_loader(c, [&](auto ld) {
-            hipLaunchKernelGGL(kh::fmt_tiles_kernel<decltype(ld)>, dim3((unsigned)n), dim3(kh::BLOCK), lds, c->stream, ld, c->cap, c->k,
+        with_loader(c, ts.sorted, ts.sorted_n, [&](auto ld, u64 slots) {
+            hipLaunchKernelGGL(kh::fmt_tiles_kernel<decltype(ld)>, dim3((unsigned)n), dim3(kh::BLOCK), lds, c->stream, ld, slots, c->k,
                                ts.format, ts.min_count, s, (const u64 *)c->ts_boff, (const u64 *)c->ts_roff, d);
         });
         s += n;
@@ -196,15 +201,27 @@ extern "C" int kh_result_text_begin(kh_ctx *c, uint32_t format, uint64_t min_cou
     if (rc != KH_OK) return rc;
     auto &ts = c->ts;
     ts.on = false;
-    if (!kh::fmt_valid(format)) return fail(c, KH_ERR_BAD_ARG, "format is none of KH_OUT_FASTA / KH_OUT_TSV / KH_OUT_JSON");
+    const bool sorted = (format & KH_OUT_SORTED) != 0;
+    if ((format & ~(uint32_t)(KH_OUT_SORTED | 3u)) != 0 || !kh::fmt_valid(format & 3u))
+        return fail(c, KH_ERR_BAD_ARG, "format is none of KH_OUT_FASTA / KH_OUT_TSV / KH_OUT_JSON, alone or with KH_OUT_SORTED");
+    format &= 3u;
     if (c->cstream) HIP_TRY(c, hipStreamSynchronize(c->cstream));  // (a chunk of an earlier stream may still travel)
-    const u64 ntiles = (c->cap + kh::FMT_TILE - 1) / kh::FMT_TILE;
+    uint64_t sorted_n = 0;
+    if (sorted) {  // the stream's own copy of the result, ascending by key; the sort's scratch goes back before any chunk is placed
+        if ((rc = kh_result_size(c, min_count, &sorted_n)) != KH_OK) return rc;
+        if ((rc = ensure_buf(c, &c->ts_skey, &c->ts_skey_cap, std::max<u64>(sorted_n, 1), "hipMalloc(sorted text pairs)")) != KH_OK) return rc;
+        if ((rc = ensure_buf(c, &c->ts_scnt, &c->ts_scnt_cap, std::max<u64>(sorted_n, 1), "hipMalloc(sorted text pairs)")) != KH_OK) return rc;
+        SortScratch sc(c);
+        if ((rc = sorted_into(c, c->ts_skey, c->ts_scnt, sorted_n, min_count, sc)) != KH_OK) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    const u64 ntiles = std::max<u64>(((sorted ? sorted_n : c->cap) + kh::FMT_TILE - 1) / kh::FMT_TILE, 1);
     if ((rc = ensure_buf(c, &c->ts_trec, &c->ts_trec_cap, ntiles, "hipMalloc(text tiles)")) != KH_OK) return rc;
     if ((rc = ensure_buf(c, &c->ts_tbyt, &c->ts_tbyt_cap, ntiles, "hipMalloc(text tiles)")) != KH_OK) return rc;
     if ((rc = ensure_buf(c, &c->ts_roff, &c->ts_roff_cap, ntiles + 1, "hipMalloc(text tiles)")) != KH_OK) return rc;
     if ((rc = ensure_buf(c, &c->ts_boff, &c->ts_boff_cap, ntiles + 1, "hipMalloc(text tiles)")) != KH_OK) return rc;
-    with_loader(c, [&](auto ld) {
-        hipLaunchKernelGGL(kh::fmt_size_kernel<decltype(ld)>, dim3(grid_for(ntiles * kh::BLOCK)), dim3(kh::BLOCK), 0, c->stream, ld, c->cap,
+    with_loader(c, sorted, sorted_n, [&](auto ld, u64 slots) {
+        hipLaunchKernelGGL(kh::fmt_size_kernel<decltype(ld)>, dim3(grid_for(ntiles * kh::BLOCK)), dim3(kh::BLOCK), 0, c->stream, ld, slots,
                            c->k, format, (u64)min_count, ntiles, c->ts_trec, c->ts_tbyt);
     });
     HIP_TRY(c, hipGetLastError());
@@ -221,6 +238,8 @@ extern "C" int kh_result_text_begin(kh_ctx *c, uint32_t format, uint64_t min_cou
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     ts.format = format;
     ts.min_count = min_count;
+    ts.sorted = sorted;
+    ts.sorted_n = sorted_n;
     ts.ntiles = ntiles;
     ts.n_records = nrec;
     ts.rec_bytes = ts.toff[ntiles];

@@ -151,7 +151,7 @@ namespace kh {
 //   fmt_tiles_kernel   one workgroup per tile: record lengths -> offsets inside the tile (wave scan by __shfl_up over the lanes'
 //                      byte sums, then the four waves' totals through LDS) -> records formatted into an LDS staging buffer ->
 //                      the tile's text stored with aligned 16-byte stores; only the unaligned head and tail go out byte-wise
-// Both read either table form: LOAD says how a slot gives (key, count).
+// Both read either table form, or a sorted array of pairs: LOAD says how a slot gives (key, count).
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int FMT_TILE = 2 * BLOCK;  // 512 slots: the worst case -- json, k = 32, 20-digit counts: 91 B per slot -- is 46,592 B of LDS
 
@@ -192,7 +192,20 @@ struct FmtNarrow {  // the 8-byte image: count << 32 | payload; the key comes ba
     }
 };
 
-// kernel-resource-usage (gfx950, hipcc -O3): 24 VGPRs, 60 / 70 SGPRs (narrow / wide), 32 B LDS, no scratch, no spills, 8 waves per SIMD.
+struct FmtSorted {  // a sorted stream's pairs (sort.hip): every one of the `cap` entries is a record, the min_count filter is already applied
+    const u64 *keys, *counts;
+    __device__ __forceinline__ void load2(u64 i, u64 cap, u64 min_count, u64 (&key)[2], u64 (&cnt)[2], bool (&live)[2]) const {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            live[j] = i + j < cap;
+            key[j] = live[j] ? keys[i + j] : 0ull;
+            cnt[j] = live[j] ? counts[i + j] : 0ull;
+        }
+    }
+};
+
+// kernel-resource-usage (gfx950, hipcc -O3): 24 VGPRs, 60 / 70 SGPRs (narrow / wide), 32 B LDS, no scratch, no spills, 8 waves per SIMD
+// (FmtSorted: 20 VGPRs, 64 SGPRs).
 template <typename LOAD>
 __global__ __launch_bounds__(BLOCK) void fmt_size_kernel(LOAD ld, u64 cap, uint32_t k, uint32_t format, u64 min_count, u64 ntiles,
                                                          uint32_t *__restrict__ tile_records, uint32_t *__restrict__ tile_bytes) {
@@ -229,7 +242,7 @@ __global__ __launch_bounds__(BLOCK) void fmt_size_kernel(LOAD ld, u64 cap, uint3
 // One workgroup per tile t0 + blockIdx.x; the text of tile t goes to out + (tile_off[t] - tile_off[t0]).
 // LDS: dynamic, 16 + FMT_TILE * record_len_max(format, k) bytes (fasta at k = 21: 22,544 B = 22.0 KiB -> 7 workgroups = 28 waves per CU of
 // 160 KiB; the worst case, json at k = 32: 45.5 KiB -> 3 workgroups = 12 waves) plus 16 B static.
-// kernel-resource-usage (gfx950, hipcc -O3): 56 / 58 VGPRs (narrow / wide), 56 SGPRs, no scratch, no spills: registers allow 8 waves
+// kernel-resource-usage (gfx950, hipcc -O3): 56 / 58 / 56 VGPRs (narrow / wide / sorted), 56 SGPRs, no scratch, no spills: registers allow 8 waves
 // per SIMD, so the dynamic LDS above is what sets the occupancy.
 template <typename LOAD>
 __global__ __launch_bounds__(BLOCK) void fmt_tiles_kernel(LOAD ld, u64 cap, uint32_t k, uint32_t format, u64 min_count, u64 t0,

@@ -681,12 +681,9 @@ extern "C" int kh_result_size(kh_ctx *c, uint64_t min_count, uint64_t *n) {
     return KH_OK;
 }
 
-extern "C" int kh_result_copy_device(kh_ctx *c, uint64_t *d_keys, uint64_t *d_counts, uint64_t cap,
-                                     uint64_t min_count, uint64_t *n) {
-    int rc = enter(c, true, true, false, true);
-    if (rc != KH_OK) return rc;
-    if (!n || (cap && (!d_keys || !d_counts))) return fail(c, KH_ERR_BAD_ARG, "NULL output");
-    rc = zero_cursors(c);
+namespace khi {
+int compact_pairs(kh_ctx *c, u64 *d_keys, u64 *d_counts, u64 cap, u64 min_count, u64 *n) {
+    int rc = zero_cursors(c);
     if (rc != KH_OK) return rc;
     if (c->narrow)  // (keys come back through the inverse hash, slot by slot)
         hipLaunchKernelGGL(kh::ntable_compact_kernel, dim3(grid_for(c->cap)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)c->ntab,
@@ -701,6 +698,15 @@ extern "C" int kh_result_copy_device(kh_ctx *c, uint64_t *d_keys, uint64_t *d_co
     *n = cur < cap ? cur : cap;
     if (cur > cap) return fail(c, KH_ERR_RANGE, "output arrays too small");
     return KH_OK;
+}
+}  // namespace khi
+
+extern "C" int kh_result_copy_device(kh_ctx *c, uint64_t *d_keys, uint64_t *d_counts, uint64_t cap,
+                                     uint64_t min_count, uint64_t *n) {
+    int rc = enter(c, true, true, false, true);
+    if (rc != KH_OK) return rc;
+    if (!n || (cap && (!d_keys || !d_counts))) return fail(c, KH_ERR_BAD_ARG, "NULL output");
+    return compact_pairs(c, (u64 *)d_keys, (u64 *)d_counts, cap, min_count, (u64 *)n);
 }
 
 extern "C" int kh_result_copy(kh_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t cap, uint64_t min_count,

@@ -26,7 +26,7 @@ static const char *USAGE =
     "                      [--min-kmers <N>] [--min-fraction <F>] [-v] [-q]\n"
     "       kmerust compare <INDEX_A> <INDEX_B> [--min-count-a <N>] [--min-count-b <N>] [-f tsv|json]\n"
     "       kmerust combine <intersect|union|subtract|count-subtract> <INDEX_A> <INDEX_B> [-c min|max|sum|left|right]\n"
-    "                       [--min-count-a <N>] [--min-count-b <N>] [-m <MIN_COUNT>] [-f <FORMAT>] [--save <SAVE>] [-q]\n"
+    "                       [--min-count-a <N>] [--min-count-b <N>] [-m <MIN_COUNT>] [-f <FORMAT>] [--save <SAVE>] [--sorted] [-q]\n"
     "\n"
     "Arguments:\n"
     "  <K>     K-mer length (1-32)\n"
@@ -41,6 +41,8 @@ static const char *USAGE =
     "  -Q, --min-quality <MIN_QUALITY>    Minimum Phred quality score (0-93) for FASTQ bases\n"
     "      --gpus <N>                     Count on the first N GPUs of the node (RCCL merge of the per-GPU tables) [default: 1]\n"
     "      --devices <LIST>               The same with explicit HIP device ordinals, e.g. 0,2,5\n"
+    "      --sorted                       Records (and the pairs of --save) in ascending k-mer order, sorted on the device:\n"
+    "                                     the same input gives the same bytes.  Changes nothing for -f histogram\n"
     "\n"
     "query --sequences: the index's count of the k-mer at every base of the sequences in <PATH>, one line per record.\n"
     "  -f summary (default)  {record}\\t{windows}\\t{present}\\t{min}\\t{max}\\t{sum}\n"
@@ -279,7 +281,7 @@ static int run_two_indexes(int argc, char **argv, bool combine) {
     const std::string usage = combine ? "Usage: kmerust combine <OP> <INDEX_A> <INDEX_B>" : "Usage: kmerust compare <INDEX_A> <INDEX_B>";
     std::vector<std::string> pos;
     std::string save;
-    bool quiet = false, json = false;
+    bool quiet = false, json = false, sorted = false;
     OutputFormat fmt = combine ? OutputFormat::Fasta : OutputFormat::Tsv;
     uint32_t calc = KH_CALC_SUM;
     const char *calc_name = "sum";
@@ -323,6 +325,8 @@ static int run_two_indexes(int argc, char **argv, bool combine) {
             min_count = parse_u64(value_of(i, a, "--min-count <MIN_COUNT>"), "--min-count <MIN_COUNT>", UINT64_MAX);
         } else if (combine && key == "--save") {
             save = value_of(i, a, "--save <SAVE>");
+        } else if (combine && a == "--sorted") {
+            sorted = true;
         } else if (a.size() > 1 && a[0] == '-' && a != "-") {
             usage_error("unexpected argument '" + a + "' found");
         } else if (pos.size() < (combine ? 3u : 2u)) {
@@ -364,7 +368,7 @@ static int run_two_indexes(int argc, char **argv, bool combine) {
     try {
         if (combine) {
             uint64_t n = 0;
-            combine_indexes(op, calc, ia, ib, min_a, min_b, min_count, fmt, save, stdout, &n);
+            combine_indexes(op, calc, ia, ib, min_a, min_b, min_count, fmt, save, stdout, &n, sorted);
             if (!quiet && !save.empty()) fprintf(stderr, "saved: %s (%llu k-mers)\n", save.c_str(), (unsigned long long)n);
         } else {
             compare_indexes(ia, ib, min_a, min_b, json, stdout);
@@ -447,7 +451,7 @@ int cli_main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "__parse")) return run_parse_dump(argc, argv);
 
     std::string k_arg, path = "-", save;
-    bool have_k = false, have_path = false, quiet = false;
+    bool have_k = false, have_path = false, quiet = false, sorted = false;
     OutputFormat fmt = OutputFormat::Fasta;
     const char *fmt_name = "fasta";
     SequenceFormat in_fmt = SequenceFormat::Auto;
@@ -493,6 +497,8 @@ int cli_main(int argc, char **argv) {
             min_quality = (int)parse_u64(value_of(i, a, "--min-quality <MIN_QUALITY>"), "--min-quality <MIN_QUALITY>", 255);
         } else if (key == "--save") {
             save = value_of(i, a, "--save <SAVE>");
+        } else if (a == "--sorted") {
+            sorted = true;
         } else if (key == "--gpus") {
             const uint64_t n = parse_u64(value_of(i, a, "--gpus <N>"), "--gpus <N>", 64);
             if (n == 0) usage_error("invalid value '0' for '--gpus <N>': at least one GPU is needed");
@@ -572,7 +578,7 @@ int cli_main(int argc, char **argv) {
 #endif
     try {
         KmerCounter kc;
-        kc.k(k).min_count(min_count).format(fmt).input_format(in_fmt).min_quality(min_quality).devices(devices);
+        kc.k(k).min_count(min_count).format(fmt).input_format(in_fmt).min_quality(min_quality).devices(devices).sorted(sorted);
         if (const char *h = getenv("KMERHIP_CAPACITY_HINT")) kc.capacity_hint(strtoull(h, nullptr, 10));
         if (!save.empty()) {  // src/main.rs:155-212: the index holds ALL k-mers, stdout honours --min-count
             bool saved = false;  // (one count: the pairs for the index, then stdout -- device text where the format has it)

@@ -29,6 +29,9 @@
 // ... and of `compare` / `combine`
 #pragma weak kh_compare
 #pragma weak kh_combine_into
+// ... and of `--sorted`: without them the pairs come through kh_result_copy and are sorted on the host
+#pragma weak kh_result_sorted
+#pragma weak kh_result_sorted_device
 
 namespace kmerust {
 
@@ -256,9 +259,10 @@ struct Session {
     kh_group *group = nullptr;
     kh_ctx *ctx = nullptr;  // ctxs[0]
     uint32_t k;
+    bool sorted;  // KmerCounter::sorted: result() and write_text() give ascending key order
     size_t next_ctx = 0;
     // input_bytes: the size of the (plain) file about to be counted, 0 = unknown -- kh_config::input_mib
-    Session(const KmerCounter &kc, bool use_qual, uint64_t input_bytes = 0) : k((uint32_t)kc.k_) {
+    Session(const KmerCounter &kc, bool use_qual, uint64_t input_bytes = 0) : k((uint32_t)kc.k_), sorted(kc.sorted_) {
         if (!kc.k_set_) throw Error("k-mer length not set");
         Lap lap(timing().create_s);
         kh_config cfg;
@@ -802,8 +806,32 @@ struct Session {
             }
         }
     }
+    // sorted: every context's pairs ascending (kh_result_sorted; kh_result_copy and a host sort where the library lacks it), and
+    // for several contexts an N-way merge of their disjoint lists on the host -- correct, not fast: the device does not order
+    // pairs across ranks.
     PackedCounts result(uint64_t min_count) {
         Lap lap(timing().result_s);
+        if (sorted) {
+            std::vector<PackedCounts> lists(ctxs.size());
+            for (size_t i = 0; i < ctxs.size(); ++i) {
+                PackedCounts &l = lists[i];
+                l.k = k;
+                uint64_t n = 0, got = 0;
+                check_on(ctxs[i], kh_result_size(ctxs[i], min_count, &n), "kh_result_size");
+                l.keys.resize(n);
+                l.counts.resize(n);
+                if (kh_result_sorted) {
+                    check_on(ctxs[i], kh_result_sorted(ctxs[i], l.keys.data(), l.counts.data(), n, min_count, &got), "kh_result_sorted");
+                } else {
+                    check_on(ctxs[i], kh_result_copy(ctxs[i], l.keys.data(), l.counts.data(), n, min_count, &got), "kh_result_copy");
+                }
+                l.keys.resize(got);
+                l.counts.resize(got);
+                if (!kh_result_sorted) sort_pairs(l);
+            }
+            if (lists.size() == 1) return std::move(lists[0]);
+            return merge_sorted(k, lists);
+        }
         PackedCounts pc;
         pc.k = k;
         std::vector<uint64_t> ns(ctxs.size(), 0);
@@ -832,10 +860,12 @@ struct Session {
         if (!kh_result_text_begin || !kh_result_text_next) return false;  // (a library without the entry points: make asan's stub)
         const char *e = getenv("KMERUST_HOST_FORMAT");
         if (e && e[0] && e[0] != '0') return false;
+        if (sorted && (ctxs.size() > 1 || !kh_result_sorted)) return false;  // (one stream per shard is not one order: result() merges)
         return fmt == OutputFormat::Fasta || fmt == OutputFormat::Tsv || (fmt == OutputFormat::Json && ctxs.size() == 1);
     }
     void write_text(FILE *out, OutputFormat fmt, uint64_t min_count) {
-        const uint32_t f = fmt == OutputFormat::Fasta ? KH_OUT_FASTA : fmt == OutputFormat::Tsv ? KH_OUT_TSV : KH_OUT_JSON;
+        const uint32_t f = (fmt == OutputFormat::Fasta ? KH_OUT_FASTA : fmt == OutputFormat::Tsv ? KH_OUT_TSV : KH_OUT_JSON) |
+                           (sorted ? KH_OUT_SORTED : 0u);
         timing().device_writer = true;
         for (kh_ctx *c : ctxs) {
             uint64_t nbytes = 0;
@@ -1241,7 +1271,7 @@ void compare_indexes(const std::string &index_a, const std::string &index_b, uin
 }
 
 void combine_indexes(uint32_t op, uint32_t calc, const std::string &index_a, const std::string &index_b, uint64_t min_a, uint64_t min_b,
-                     uint64_t min_count, OutputFormat fmt, const std::string &save, FILE *out, uint64_t *n_pairs) {
+                     uint64_t min_count, OutputFormat fmt, const std::string &save, FILE *out, uint64_t *n_pairs, bool sorted) {
     if (!kh_combine_into || !kh_merge_pairs)
         throw Error("combine needs a kmerhip library with kh_combine_into and kh_merge_pairs; the one this program was built against has neither");
     PackedCounts pa, pb;
@@ -1249,7 +1279,7 @@ void combine_indexes(uint32_t op, uint32_t calc, const std::string &index_a, con
     IndexTable a(pa, -1), b(pb, -1);
     const uint64_t na = pa.keys.size(), nb = pb.keys.size();
     KmerCounter kc;
-    kc.k(pa.k).capacity_hint(op == KH_SET_UNION ? na + nb : op == KH_SET_INTERSECT ? std::min(na, nb) : na);
+    kc.k(pa.k).capacity_hint(op == KH_SET_UNION ? na + nb : op == KH_SET_INTERSECT ? std::min(na, nb) : na).sorted(sorted);
     pa = PackedCounts();  // (the host copies are no longer needed)
     pb = PackedCounts();
     Session s(kc, false);

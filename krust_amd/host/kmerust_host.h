@@ -11,11 +11,14 @@
 //   CLI                                            src/cli.rs:33-144, src/main.rs:34-299
 // Counting itself always goes through kh_* (the HIP path); there is no CPU counting here.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
 #include <map>
+#include <numeric>
+#include <queue>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -82,6 +85,9 @@ public:
     // No reference counterpart (the reference is one process on CPU cores): count on several GPUs of the node,
     // one table per device, merged by the library's RCCL exchange (kh_group_*) into a table sharded by hash range.
     KmerCounter &devices(std::vector<int> d) { devices_ = std::move(d); return *this; }
+    // No reference counterpart (HashMap order is unspecified there): records and index pairs in ascending key order -- the k-mer
+    // strings in lexicographic order --, so that the same input gives the same bytes (`kmerust --sorted`).  Sorted on the device.
+    KmerCounter &sorted(bool s) { sorted_ = s; return *this; }
 
     // count(): HashMap<String,u64> filtered by min_count (builder.rs:242-262)
     std::unordered_map<std::string, uint64_t> count(const std::string &path) const;
@@ -110,7 +116,46 @@ private:
     uint64_t capacity_hint_ = 0;
     int device_ = -1;
     std::vector<int> devices_;
+    bool sorted_ = false;
 };
+
+// ---- pairs in ascending key order on the host (`--sorted` where the device cannot give the whole order) ----------------------
+// N lists, each ascending by key, with pairwise disjoint key sets (the shards of a multi-GPU merge, each from kh_result_sorted)
+// into one ascending list: an N-way merge over a heap of the lists' heads.  Correct, not fast: one heap step per pair.
+inline PackedCounts merge_sorted(uint32_t k, const std::vector<PackedCounts> &lists) {
+    PackedCounts out;
+    out.k = k;
+    size_t total = 0;
+    for (const PackedCounts &l : lists) total += l.keys.size();
+    out.keys.reserve(total);
+    out.counts.reserve(total);
+    using Head = std::pair<uint64_t, size_t>;  // (key, list)
+    std::priority_queue<Head, std::vector<Head>, std::greater<Head>> heap;
+    std::vector<size_t> pos(lists.size(), 0);
+    for (size_t i = 0; i < lists.size(); ++i)
+        if (!lists[i].keys.empty()) heap.push({lists[i].keys[0], i});
+    while (!heap.empty()) {
+        const size_t i = heap.top().second;
+        heap.pop();
+        out.keys.push_back(lists[i].keys[pos[i]]);
+        out.counts.push_back(lists[i].counts[pos[i]]);
+        if (++pos[i] < lists[i].keys.size()) heap.push({lists[i].keys[pos[i]], i});
+    }
+    return out;
+}
+// Pairs in any order into ascending key order, each count with its key (a library without kh_result_sorted: kh_result_copy, then this).
+inline void sort_pairs(PackedCounts &pc) {
+    std::vector<size_t> order(pc.keys.size());
+    std::iota(order.begin(), order.end(), (size_t)0);
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return pc.keys[a] < pc.keys[b]; });
+    std::vector<uint64_t> keys(order.size()), counts(order.size());
+    for (size_t i = 0; i < order.size(); ++i) {
+        keys[i] = pc.keys[order[i]];
+        counts[i] = pc.counts[order[i]];
+    }
+    pc.keys.swap(keys);
+    pc.counts.swap(counts);
+}
 
 // ---- phase walls of the last count (KMERUST_TIMING=1 makes the CLI print them as one JSON line on stderr) ---------
 // Stands where the reference has its tracing spans "read_sequences" / "process_sequences" / "unpack_kmers"
@@ -211,7 +256,8 @@ void compare_indexes(const std::string &index_a, const std::string &index_b, uin
 // through the writers of the counting command: `save` (unless empty) takes ALL result pairs as an index, `out` the records with
 // count >= min_count in format `fmt` (the device text stream where the format has one).  *n_pairs (optional): pairs produced.
 void combine_indexes(uint32_t op, uint32_t calc, const std::string &index_a, const std::string &index_b, uint64_t min_a, uint64_t min_b,
-                     uint64_t min_count, OutputFormat fmt, const std::string &save, FILE *out, uint64_t *n_pairs = nullptr);
+                     uint64_t min_count, OutputFormat fmt, const std::string &save, FILE *out, uint64_t *n_pairs = nullptr,
+                     bool sorted = false);  // sorted: records and index pairs in ascending key order, as KmerCounter::sorted
 
 // ---- KMIX index (src/index.rs) -----------------------------------------------------------------
 uint32_t crc32_ieee(const uint8_t *data, size_t n, uint32_t crc = 0);  // src/index.rs:404-431

@@ -26,6 +26,7 @@ KH_ERR_RCCL = -10
 KH_ERR_PEER = -11
 TEXT_FASTA, TEXT_FASTQ = 1, 2
 KH_OUT_FASTA, KH_OUT_TSV, KH_OUT_JSON = 1, 2, 3  # kh_result_text_begin
+KH_OUT_SORTED = 0x100  # ... ORed into the format: records in ascending key order
 PROFILE_NO_WINDOW = 0xFFFFFFFF  # KH_PROFILE_NO_WINDOW: an entry of kh_profile* where counting would see no window
 # KH_REC_*: the words of a row of kh_profile_records*
 REC_WORDS = 8
@@ -88,6 +89,8 @@ SYMBOLS = {
     "kh_result_size": (C.c_int, [_P, _U64, C.POINTER(_U64)]),
     "kh_result_copy": (C.c_int, [_P, _P, _P, _U64, _U64, C.POINTER(_U64)]),
     "kh_result_copy_device": (C.c_int, [_P, _P, _P, _U64, _U64, C.POINTER(_U64)]),
+    "kh_result_sorted": (C.c_int, [_P, _P, _P, _U64, _U64, C.POINTER(_U64)]),
+    "kh_result_sorted_device": (C.c_int, [_P, _P, _P, _U64, _U64, C.POINTER(_U64)]),
     "kh_result_text_begin": (C.c_int, [_P, C.c_uint32, _U64, C.POINTER(_U64), C.POINTER(_U64)]),
     "kh_result_text_next": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
     "kh_result_text_next_device": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
@@ -318,6 +321,23 @@ class DeviceCounter:
         self._check(lib().kh_result_copy_device(self._h, d_keys, d_counts, int(cap), int(min_count), C.byref(got)))
         return int(got.value)
 
+    def result_sorted(self, min_count=1):
+        """(keys, counts) ascending by key, sorted on the device (kh_result_sorted): the k-mer strings in lexicographic order."""
+        n = self.result_size(min_count)
+        keys = np.empty(n, dtype=np.uint64)
+        cnts = np.empty(n, dtype=np.uint64)
+        got = _U64(0)
+        self._check(lib().kh_result_sorted(self._h, keys.ctypes.data if n else None, cnts.ctypes.data if n else None, n,
+                                           int(min_count), C.byref(got)))
+        assert got.value == n
+        return keys, cnts
+
+    def result_sorted_device(self, d_keys, d_counts, cap, min_count=1):
+        """The same into device arrays of capacity cap (KH_ERR_RANGE, nothing written, when the result is larger)."""
+        got = _U64(0)
+        self._check(lib().kh_result_sorted_device(self._h, d_keys, d_counts, int(cap), int(min_count), C.byref(got)))
+        return int(got.value)
+
     def as_dict(self, min_count=1):
         k, c = self.result(min_count)
         return dict(zip(k.tolist(), c.tolist()))
@@ -327,11 +347,13 @@ class DeviceCounter:
         return {unpack(key, self.k): c for key, c in self.as_dict(min_count).items()}
 
     # -- output as text, formatted on the device -----------------------------
-    def result_text_begin(self, format, min_count=1):
+    def result_text_begin(self, format, min_count=1, sorted=False):
         """Starts (or restarts) the text stream of the records with count >= min_count; format: "fasta" | "tsv" | "json".
+        sorted: the records come in ascending key order (KH_OUT_SORTED) instead of table-slot order.
         Returns (n_records, n_bytes) of the whole stream."""
         nr, nb = _U64(0), _U64(0)
-        self._check(lib().kh_result_text_begin(self._h, _out_format(format), int(min_count), C.byref(nr), C.byref(nb)))
+        fmt = _out_format(format) | (KH_OUT_SORTED if sorted else 0)
+        self._check(lib().kh_result_text_begin(self._h, fmt, int(min_count), C.byref(nr), C.byref(nb)))
         return int(nr.value), int(nb.value)
 
     def result_text_next(self, buf, cap=None):
@@ -347,10 +369,10 @@ class DeviceCounter:
         self._check(lib().kh_result_text_next(self._h, addr, cap, C.byref(n)))
         return int(n.value)
 
-    def result_text(self, format, min_count=1, piece_bytes=8 << 20):
+    def result_text(self, format, min_count=1, piece_bytes=8 << 20, sorted=False):
         """Generator over the table as text: `bytes` pieces of at most piece_bytes that end at record ends and whose
         concatenation is the whole document (the reference's output_counts, src/run.rs:441-486, formatted on the device)."""
-        self.result_text_begin(format, min_count)
+        self.result_text_begin(format, min_count, sorted=sorted)
         buf = np.empty(max(int(piece_bytes), 1), dtype=np.uint8)
         while True:
             n = self.result_text_next(buf)
