@@ -114,6 +114,12 @@ pub mod sys {
         /// `count[key] += c` in `dst` for the pairs of a set operation of `a` and `b` (op: KH_SET_*, calc: KH_CALC_*)
         pub fn kh_combine_into(dst: *mut KhCtx, a: *mut KhCtx, b: *mut KhCtx, op: u32, calc: u32, min_a: u64, min_b: u64,
                                n_pairs: *mut u64) -> c_int;
+        /// the table against itself (de Bruijn degrees), read only: `out` takes the 258 words KH_GRAPH_* of the header names --
+        /// `out[m]`, m < 256: the nodes whose neighbour mask is m; then the nodes and the sum of their counts
+        pub fn kh_graph_stats(ctx: *mut KhCtx, min_count: u64, out: *mut u64) -> c_int;
+        /// `masks[i]` = the neighbour mask of the packed canonical key `keys[i]`: bit c = right neighbour by letter c, bit 4 + c = left
+        pub fn kh_graph_masks_device(ctx: *mut KhCtx, d_keys: *const u64, n: u64, min_count: u64, d_masks: *mut u8) -> c_int;
+        pub fn kh_graph_masks(ctx: *mut KhCtx, keys: *const u64, n: u64, min_count: u64, masks: *mut u8) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
         pub fn kh_result_sorted(ctx: *mut KhCtx, keys: *mut u64, counts: *mut u64, cap: u64,
                                 min_count: u64, n: *mut u64) -> c_int;
@@ -183,6 +189,15 @@ impl TableComparison {
     pub fn containment_b(&self) -> f64 { self.shared as f64 / self.distinct_b as f64 }
     pub fn bray_curtis(&self) -> f64 { 1.0 - 2.0 * self.sum_min as f64 / (self.sum_a as f64 + self.sum_b as f64) }
 }
+
+/// `KH_GRAPH_WORDS`: the words of `kh_graph_stats` -- 256 mask counters, then `KH_GRAPH_NODES` and `KH_GRAPH_KMERS`.
+pub const GRAPH_WORDS: usize = 258;
+pub const GRAPH_NODES: usize = 256;
+pub const GRAPH_KMERS: usize = 257;
+/// `KH_GRAPH_RIGHT(c)`: the mask bit of the right neighbour by letter `c` (0..3 = A, C, G, T) of a key's canonical string.
+pub const fn graph_right(c: u32) -> u8 { 1u8 << c }
+/// `KH_GRAPH_LEFT(c)`: ... of the left neighbour.
+pub const fn graph_left(c: u32) -> u8 { 16u8 << c }
 
 /// KH_SET_*: the set operation of `kh_combine_into`.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -451,6 +466,24 @@ impl HipKmerMap {
         let mut n = 0u64;
         check(self.ctx, unsafe { sys::kh_combine_into(self.ctx, a.ctx, b.ctx, op as u32, calc as u32, min_a, min_b, &mut n) })?;
         Ok(n)
+    }
+
+    /// The de Bruijn graph degrees of this table (`kh_graph_stats`), read only: over the node set S = the keys with a count of
+    /// at least `max(min_count, 1)`, word `m` (m < 256) counts the nodes whose neighbour mask is `m`, word [`GRAPH_NODES`] is
+    /// |S| and word [`GRAPH_KMERS`] the sum of their counts.
+    pub fn graph_stats(&self, min_count: u64) -> Result<Vec<u64>, HipError> {
+        let mut w = vec![0u64; GRAPH_WORDS];
+        check(self.ctx, unsafe { sys::kh_graph_stats(self.ctx, min_count, w.as_mut_ptr()) })?;
+        Ok(w)
+    }
+
+    /// One neighbour mask per packed canonical key (`kh_graph_masks`): bit `c` ([`graph_right`]) is set iff the right neighbour
+    /// by letter `c` is in S, bit `4 + c` ([`graph_left`]) iff the left one is; a word that is no canonical key of this k gets 0.
+    /// The keys need not be in S.  With the keys of [`sorted_pairs`](Self::sorted_pairs) the masks line up with those pairs.
+    pub fn graph_masks(&self, keys: &[u64], min_count: u64) -> Result<Vec<u8>, HipError> {
+        let mut m = vec![0u8; keys.len()];
+        check(self.ctx, unsafe { sys::kh_graph_masks(self.ctx, keys.as_ptr(), keys.len() as u64, min_count, m.as_mut_ptr()) })?;
+        Ok(m)
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

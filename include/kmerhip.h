@@ -361,6 +361,45 @@ int kh_compare(kh_ctx *a, kh_ctx *b, uint64_t min_a, uint64_t min_b, uint64_t *o
 int kh_combine_into(kh_ctx *dst, kh_ctx *a, kh_ctx *b, uint32_t op, uint32_t calc,
                     uint64_t min_a, uint64_t min_b, uint64_t *n_pairs /* may be NULL */);
 
+/* ---- de Bruijn graph degrees of a count table (no reference counterpart) --- */
+/* What unitig / contig construction (BCALM, Cuttlefish after KMC), tip clipping, bubble popping, branch-point counts and walks
+ * from a seed ask of a k-mer table: which of the four possible successors and four possible predecessors of a k-mer are also
+ * there.  The table is read against itself on the device -- eight probes per k-mer, one byte out.
+ * NODE SET S: for this context's k and a min_count, the canonical keys whose count is at least max(min_count, 1).
+ * MASK of a packed canonical key x: let s be its k-letter string and canon() = min(forward, reverse complement).  One byte:
+ *   bit c     (c = 0..3 for A, C, G, T), KH_GRAPH_RIGHT(c), is set iff canon(s[1:] + c) is in S;
+ *   bit 4 + c,                           KH_GRAPH_LEFT(c),  is set iff canon(c + s[:-1]) is in S.
+ * ORIENTATION: left and right refer to x's canonical string.
+ * SPECIAL CASES: none.  A homopolymer is its own neighbour, a palindrome is possible at even k, at k = 1 every present key is
+ * everyone's neighbour: all of it follows the two formulas.
+ * BIT ARITHMETIC, with r = the reverse complement of x and m = the mask of the low 2k bits:
+ *   right neighbour: forward ((x << 2) | c) & m,       reverse (r >> 2) | ((3 - c) << 2(k-1));
+ *   left neighbour:  forward (x >> 2) | (c << 2(k-1)), reverse ((r << 2) | (3 - c)) & m.
+ * KEYS OUTSIDE S: x need not be in S -- the mask of an absent or below-threshold key is still its extensions into S (what a
+ * graph walk asks).
+ * INVALID WORDS: a word that is not a canonical key of this k -- a bit at or above 2k, or greater than its reverse complement --
+ * gets mask 0.
+ * kh_graph_stats fills KH_GRAPH_WORDS words of host memory: out[m], m < 256 = the nodes of S whose mask is m, then |S| and the
+ * sum of the counts over S.  kh_graph_masks_device writes masks[i] = the mask of keys[i] for all n keys in this device's memory:
+ * keys at any alignment, every one of the n bytes written (d_masks at any alignment), complete when it returns -- the key array
+ * is typically what kh_result_copy_device / kh_result_sorted_device just produced, so that the masks line up with those pairs.
+ * kh_graph_masks is the host form, built like kh_lookup: device scratch for the call, one launch, copy back; no memory for it is
+ * KH_ERR_OOM and leaves the context usable.
+ * CONTRACT.  All three only READ, like kh_lookup and kh_compare: pending pushes are counted first, the table is read in the form
+ * it is in (kh_stats.slot_bytes stays what it was), no count changes, a kh_result_text_* stream in progress goes on, and a bad
+ * argument (NULL with n > 0, a NULL out: KH_ERR_BAD_ARG) leaves the context usable.  n == 0 is KH_OK, and the arrays may then
+ * be NULL.
+ * SHARDS (kh_set_shard, or after a merge across more than one rank): the neighbours of a shard's keys live on other owners, so
+ * all three calls return KH_ERR_STATE with a message; the context stays usable. */
+#define KH_GRAPH_RIGHT(c) (1u << (c))
+#define KH_GRAPH_LEFT(c) (16u << (c))
+#define KH_GRAPH_WORDS 258
+#define KH_GRAPH_NODES 256   /* |S| */
+#define KH_GRAPH_KMERS 257   /* sum of the counts over S, modulo 2^64 */
+int kh_graph_stats(kh_ctx *ctx, uint64_t min_count, uint64_t *out /* KH_GRAPH_WORDS, host */);
+int kh_graph_masks_device(kh_ctx *ctx, const uint64_t *d_keys, uint64_t n, uint64_t min_count, uint8_t *d_masks);
+int kh_graph_masks(kh_ctx *ctx, const uint64_t *keys, uint64_t n, uint64_t min_count, uint8_t *masks);
+
 /* ---- multi-GPU merge (no reference counterpart) ----------- */
 /* Owner shard of a packed canonical k-mer among nparts shards: a fast-range of the top bits of
  * the table hash, so a shard is a contiguous range of table regions (same function on host and

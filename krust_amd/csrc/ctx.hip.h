@@ -8,6 +8,7 @@
 //   format.hip    kh_result_text_*: the table formatted as text on the device and streamed out in pieces
 //   profile.hip   kh_profile*: the table's count at every window start of new sequences
 //   join.hip      kh_compare / kh_combine_into: one table scanned, another probed, statistics or a third table out
+//   graph.hip     kh_graph_stats / kh_graph_masks*: the table against itself, eight probes per k-mer, its de Bruijn degrees out
 //   sort.hip      kh_result_sorted*: the result pairs in ascending key order (a device radix sort; format.hip streams it as text)
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
@@ -330,6 +331,8 @@ struct kh_ctx {
     u64 *pr_rec = nullptr;        u64 pr_rec_cap = 0;   // offsets
     // kh_compare / kh_combine_into (join.hip): the words the launching context's kernels add up -- KH_CMP_WORDS, then the pair count
     u64 *jn_words = nullptr;
+    // kh_graph_stats (graph.hip): the KH_GRAPH_WORDS words its kernel adds up
+    u64 *gr_words = nullptr;
 
     bool poisoned = false;
     std::string last_error;

@@ -12,27 +12,7 @@
 
 namespace kh {
 
-// ---- source views: slot i of the scanned table -> (key, count), false for a free slot ---------------------------------------
-struct JsWide {
-    const Slot *table;
-    __device__ __forceinline__ bool load(u64 i, u64 &key, u64 &count) const {
-        const uint4 v = *reinterpret_cast<const uint4 *>(&table[i]);
-        key = ((u64)v.y << 32) | v.x;
-        count = ((u64)v.w << 32) | v.z;
-        return key != KH_EMPTY_KEY;
-    }
-};
-struct JsNarrow {
-    const u64 *ntab;
-    PartGeom g;
-    __device__ __forceinline__ bool load(u64 i, u64 &key, u64 &count) const {
-        const u64 sl = ntab[i];
-        count = sl >> 32;
-        const bool live = count != 0;
-        key = live ? narrow_key(g, i, (uint32_t)sl) : 0ull;  // (the inverse hash only for live slots: ntable_compact_kernel)
-        return live;
-    }
-};
+// (the source views JsWide / JsNarrow -- slot i of the scanned table -> (key, count) -- live in probe.hip.h: graph.hip scans with them too)
 
 // the null probe: every key reads as absent, nothing is loaded
 struct PbNone {

@@ -1,5 +1,5 @@
 // probe.hip.h -- a read-only probe of one table, in either of its forms: what profile.hip asks per window of new sequences
-// and join.hip per live slot of another table.
+// and join.hip per live slot of another table, and graph.hip eight times per k-mer of the same table.
 #pragma once
 #include "ctx.hip.h"
 
@@ -99,6 +99,28 @@ struct PfNarrow {
             w = r.reg[off];
         }
         return 0ull;
+    }
+};
+
+// ---- source views: slot i of a scanned table -> (key, count), false for a free slot (join.hip, graph.hip) -------------------
+struct JsWide {
+    const Slot *table;
+    __device__ __forceinline__ bool load(u64 i, u64 &key, u64 &count) const {
+        const uint4 v = *reinterpret_cast<const uint4 *>(&table[i]);
+        key = ((u64)v.y << 32) | v.x;
+        count = ((u64)v.w << 32) | v.z;
+        return key != KH_EMPTY_KEY;
+    }
+};
+struct JsNarrow {
+    const u64 *ntab;
+    PartGeom g;
+    __device__ __forceinline__ bool load(u64 i, u64 &key, u64 &count) const {
+        const u64 sl = ntab[i];
+        count = sl >> 32;
+        const bool live = count != 0;
+        key = live ? narrow_key(g, i, (uint32_t)sl) : 0ull;  // (the inverse hash only for live slots: ntable_compact_kernel)
+        return live;
     }
 };
 

@@ -32,6 +32,10 @@
 // ... and of `--sorted`: without them the pairs come through kh_result_copy and are sorted on the host
 #pragma weak kh_result_sorted
 #pragma weak kh_result_sorted_device
+// ... and of `graph`
+#pragma weak kh_graph_stats
+#pragma weak kh_graph_masks_device
+#pragma weak kh_graph_masks
 
 namespace kmerust {
 
@@ -1297,6 +1301,65 @@ void combine_indexes(uint32_t op, uint32_t calc, const std::string &index_a, con
     if (fmt == OutputFormat::Histogram) write_histogram(out, s.histogram(min_count));
     else if (s.device_text_ok(fmt)) s.write_text(out, fmt, min_count);
     else write_counts(out, s.result(min_count), fmt, 1);
+}
+
+// =============================================================================================
+// the de Bruijn graph degrees of an index
+// =============================================================================================
+void write_graph_summary(FILE *out, const uint64_t *words, bool json) {
+    const GraphSummary g = graph_summary(words);
+    std::vector<std::pair<std::string, uint64_t>> rows = {{"nodes", g.nodes}, {"kmers", g.kmers}, {"arcs", g.arcs}, {"isolated", g.isolated},
+                                                          {"dead_ends", g.dead_ends}, {"branching", g.branching}, {"simple", g.simple}};
+    for (int l = 0; l < 5; ++l)
+        for (int r = 0; r < 5; ++r) rows.push_back({"deg_" + std::to_string(l) + "_" + std::to_string(r), g.deg[l][r]});
+    if (json) {
+        fputc('{', out);
+        for (size_t i = 0; i < rows.size(); ++i) fprintf(out, "%s\"%s\": %llu", i ? ", " : "", rows[i].first.c_str(), (unsigned long long)rows[i].second);
+        fputs("}\n", out);
+    } else {
+        for (const auto &r : rows) fprintf(out, "%s\t%llu\n", r.first.c_str(), (unsigned long long)r.second);
+    }
+}
+
+void graph_index(const std::string &index, uint64_t min_count, GraphFormat fmt, bool sorted, FILE *out) {
+    if (!kh_graph_stats || !kh_graph_masks || !kh_graph_masks_device || !kh_merge_pairs)
+        throw Error("graph needs a kmerhip library with kh_graph_stats, kh_graph_masks and kh_merge_pairs; the one this program was built against has neither");
+    PackedCounts idx = load_index(index);
+    const uint32_t k = idx.k;
+    IndexTable t(idx, -1);
+    idx = PackedCounts();  // (the host copy is no longer needed)
+    if (fmt != GraphFormat::Tsv) {
+        uint64_t words[KH_GRAPH_WORDS];
+        Session::check_on(t.c, kh_graph_stats(t.c, min_count, words), "kh_graph_stats");
+        write_graph_summary(out, words, fmt == GraphFormat::Json);
+    } else {
+        uint64_t n = 0, got = 0;
+        Session::check_on(t.c, kh_result_size(t.c, min_count, &n), "kh_result_size");
+        std::vector<uint64_t> keys(n), counts(n);
+        if (sorted && kh_result_sorted) {
+            Session::check_on(t.c, kh_result_sorted(t.c, keys.data(), counts.data(), n, min_count, &got), "kh_result_sorted");
+        } else {
+            Session::check_on(t.c, kh_result_copy(t.c, keys.data(), counts.data(), n, min_count, &got), "kh_result_copy");
+        }
+        PackedCounts pc;
+        pc.k = k;
+        keys.resize(got);
+        counts.resize(got);
+        pc.keys.swap(keys);
+        pc.counts.swap(counts);
+        if (sorted && !kh_result_sorted) sort_pairs(pc);
+        std::vector<uint8_t> masks(got);
+        Session::check_on(t.c, kh_graph_masks(t.c, pc.keys.data(), got, min_count, masks.data()), "kh_graph_masks");
+        std::string text;
+        for (uint64_t i = 0; i < got; ++i) {
+            format_graph_line(text, pc.keys[i], k, pc.counts[i], masks[i]);
+            if (text.size() >= (1u << 20) || i + 1 == got) {
+                if (fwrite(text.data(), 1, text.size(), out) != text.size()) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+                text.clear();
+            }
+        }
+    }
+    if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
 }
 
 // =============================================================================================

@@ -259,6 +259,58 @@ void combine_indexes(uint32_t op, uint32_t calc, const std::string &index_a, con
                      uint64_t min_count, OutputFormat fmt, const std::string &save, FILE *out, uint64_t *n_pairs = nullptr,
                      bool sorted = false);  // sorted: records and index pairs in ascending key order, as KmerCounter::sorted
 
+// ---- the de Bruijn graph degrees of an index (`kmerust graph`; no reference counterpart) ---------------------------------------------
+// What `kmerust graph -f summary` derives from the KH_GRAPH_WORDS words of kh_graph_stats (word m < 256: the nodes whose neighbour
+// mask is m -- bits 0..3 the right neighbours by A, C, G, T, bits 4..7 the left ones).  With l / r = the number of left / right bits:
+//   deg[l][r]  nodes of left degree l and right degree r      arcs       the sum over the nodes of l + r
+//   isolated   mask 0                                         dead_ends  exactly one of l, r is 0
+//   branching  l >= 2 or r >= 2                               simple     l == 1 and r == 1
+// Sums are modulo 2^64, like the words.  Pure: no device, no library call.
+struct GraphSummary {
+    uint64_t nodes = 0, kmers = 0, arcs = 0, isolated = 0, dead_ends = 0, branching = 0, simple = 0;
+    uint64_t deg[5][5] = {};
+};
+inline GraphSummary graph_summary(const uint64_t *words) {
+    GraphSummary g;
+    g.nodes = words[KH_GRAPH_NODES];
+    g.kmers = words[KH_GRAPH_KMERS];
+    for (unsigned m = 0; m < 256; ++m) {
+        const unsigned l = (unsigned)__builtin_popcount(m >> 4), r = (unsigned)__builtin_popcount(m & 15u);
+        const uint64_t n = words[m];
+        g.deg[l][r] += n;
+        g.arcs += n * (uint64_t)(l + r);
+        if (m == 0) g.isolated += n;
+        if ((l == 0) != (r == 0)) g.dead_ends += n;
+        if (l >= 2 || r >= 2) g.branching += n;
+        if (l == 1 && r == 1) g.simple += n;
+    }
+    return g;
+}
+// One line of `kmerust graph -f tsv`, appended to dst: "{kmer}\t{count}\t{left}\t{right}\n" -- left / right: the letters of the
+// mask's set bits in ACGT order, "." when none is set.  Correct, not fast: the device has no formatter for this layout.
+inline void format_graph_line(std::string &dst, uint64_t key, uint32_t k, uint64_t count, uint8_t mask) {
+    static const char letters[5] = "ACGT";
+    for (uint32_t i = 0; i < k; ++i) dst.push_back(letters[(key >> (2 * (k - 1 - i))) & 3u]);
+    dst.push_back('\t');
+    dst += std::to_string(count);
+    for (unsigned side = 0; side < 2; ++side) {  // left (bits 4..7), then right (bits 0..3)
+        const unsigned bits = side == 0 ? (unsigned)(mask >> 4) : (unsigned)(mask & 15u);
+        dst.push_back('\t');
+        if (!bits) dst.push_back('.');
+        for (unsigned c = 0; c < 4; ++c)
+            if (bits & (1u << c)) dst.push_back(letters[c]);
+    }
+    dst.push_back('\n');
+}
+enum class GraphFormat { Summary, Tsv, Json };
+// The summary by name: nodes, kmers, arcs, isolated, dead_ends, branching, simple, then the 25 deg_{l}_{r}; tsv = one
+// "{name}\t{value}" line each, json = one object on one line.
+void write_graph_summary(FILE *out, const uint64_t *words, bool json);
+// The index into a device table (as `compare` loads one); Summary / Json: kh_graph_stats and write_graph_summary; Tsv: the pairs with
+// count >= min_count (kh_result_copy, or kh_result_sorted with `sorted`), kh_graph_masks over their keys, format_graph_line.
+// Throws Error -- also against a library without the three kh_graph_* entry points.
+void graph_index(const std::string &index, uint64_t min_count, GraphFormat fmt, bool sorted, FILE *out);
+
 // ---- KMIX index (src/index.rs) -----------------------------------------------------------------
 uint32_t crc32_ieee(const uint8_t *data, size_t n, uint32_t crc = 0);  // src/index.rs:404-431
 void save_index(const PackedCounts &pc, const std::string &path);      // gzip if path ends in .gz

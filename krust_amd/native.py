@@ -37,6 +37,19 @@ CMP_DISTINCT_A, CMP_DISTINCT_B, CMP_SHARED, CMP_SUM_A, CMP_SUM_B, CMP_SHARED_SUM
 CMP_NAMES = ("distinct_a", "distinct_b", "shared", "sum_a", "sum_b", "shared_sum_a", "shared_sum_b", "sum_min")
 SET_INTERSECT, SET_UNION, SET_SUBTRACT, SET_COUNT_SUBTRACT = 1, 2, 3, 4
 CALC_MIN, CALC_MAX, CALC_SUM, CALC_LEFT, CALC_RIGHT = 1, 2, 3, 4, 5
+# KH_GRAPH_*: the words of kh_graph_stats -- [m], m < 256: nodes whose mask is m -- and the bits of a mask (kh_graph_masks*)
+GRAPH_WORDS, GRAPH_NODES, GRAPH_KMERS = 258, 256, 257
+
+
+def GRAPH_RIGHT(c):
+    """The mask bit of the right neighbour by letter c (0..3 = A, C, G, T)."""
+    return 1 << c
+
+
+def GRAPH_LEFT(c):
+    return 16 << c
+
+
 _SET_OPS = {"intersect": SET_INTERSECT, "union": SET_UNION, "subtract": SET_SUBTRACT, "count-subtract": SET_COUNT_SUBTRACT}
 _CALCS = {"min": CALC_MIN, "max": CALC_MAX, "sum": CALC_SUM, "left": CALC_LEFT, "right": CALC_RIGHT}
 
@@ -102,6 +115,9 @@ SYMBOLS = {
     "kh_profile_records": (C.c_int, [_P, _P, _P, _U64, _P, _U64, C.c_uint32, C.c_uint32, _P]),
     "kh_compare": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_combine_into": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _U64, _U64, C.POINTER(_U64)]),
+    "kh_graph_stats": (C.c_int, [_P, _U64, _P]),
+    "kh_graph_masks_device": (C.c_int, [_P, _P, _U64, _U64, _P]),
+    "kh_graph_masks": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
     "kh_set_shard": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "kh_set_region_window": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -480,6 +496,30 @@ class DeviceCounter:
         self._check(lib().kh_combine_into(self._h, a._h, b._h, int(_SET_OPS.get(op, op)), int(_CALCS.get(calc, calc)), int(min_a),
                                           int(min_b), C.byref(n)))
         return int(n.value)
+
+    # -- the table against itself: de Bruijn graph degrees --------------------
+    def graph_stats(self, min_count=1):
+        """kh_graph_stats: a uint64 array of GRAPH_WORDS words over the node set S = the keys with a count >= max(min_count, 1) --
+        [m] for m < 256 = the nodes whose neighbour mask is m, [GRAPH_NODES] = |S|, [GRAPH_KMERS] = the sum of their counts."""
+        out = np.zeros(GRAPH_WORDS, dtype=np.uint64)
+        self._check(lib().kh_graph_stats(self._h, int(min_count), out.ctypes.data))
+        return out
+
+    def graph_masks(self, keys, min_count=1):
+        """kh_graph_masks: a uint8 array, one mask per packed canonical key -- bit c (GRAPH_RIGHT) set iff the right neighbour
+        by letter c is in S, bit 4 + c (GRAPH_LEFT) iff the left one is; 0 for a word that is no canonical key of this k.  The
+        keys need not be in S themselves.  With the keys of result() / result_sorted() the masks line up with those pairs."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros(keys.size, dtype=np.uint8)
+        self._check(lib().kh_graph_masks(self._h, keys.ctypes.data if keys.size else None, keys.size, int(min_count),
+                                         out.ctypes.data if keys.size else None))
+        return out
+
+    def graph_masks_device(self, d_keys, n, d_masks, min_count=1):
+        """The same on device memory: integer addresses or torch tensors of n uint64 keys and n bytes to fill, both at any
+        alignment.  Returns when d_masks is complete."""
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        self._check(lib().kh_graph_masks_device(self._h, ptr(d_keys), int(n), int(min_count), ptr(d_masks)))
 
     # -- multi-GPU merge ---------------------------------------------------
     def comm_init(self, nranks, rank, unique_id):
