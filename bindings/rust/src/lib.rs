@@ -120,6 +120,10 @@ pub mod sys {
         /// `masks[i]` = the neighbour mask of the packed canonical key `keys[i]`: bit c = right neighbour by letter c, bit 4 + c = left
         pub fn kh_graph_masks_device(ctx: *mut KhCtx, d_keys: *const u64, n: u64, min_count: u64, d_masks: *mut u8) -> c_int;
         pub fn kh_graph_masks(ctx: *mut KhCtx, keys: *const u64, n: u64, min_count: u64, masks: *mut u8) -> c_int;
+        pub fn kh_unitigs_begin(ctx: *mut KhCtx, min_count: u64, n_unitigs: *mut u64, n_bases: *mut u64) -> c_int;
+        pub fn kh_unitigs_copy_device(ctx: *mut KhCtx, d_rows: *mut u64, row_cap: u64, d_bases: *mut u8, base_cap: u64) -> c_int;
+        pub fn kh_unitigs_copy(ctx: *mut KhCtx, rows: *mut u64, row_cap: u64, bases: *mut u8, base_cap: u64) -> c_int;
+        pub fn kh_unitigs_end(ctx: *mut KhCtx) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
         pub fn kh_result_sorted(ctx: *mut KhCtx, keys: *mut u64, counts: *mut u64, cap: u64,
                                 min_count: u64, n: *mut u64) -> c_int;
@@ -198,6 +202,15 @@ pub const GRAPH_KMERS: usize = 257;
 pub const fn graph_right(c: u32) -> u8 { 1u8 << c }
 /// `KH_GRAPH_LEFT(c)`: ... of the left neighbour.
 pub const fn graph_left(c: u32) -> u8 { 16u8 << c }
+
+/// `KH_UNI_WORDS`: the words of a unitig row of `kh_unitigs_copy` -- `KH_UNI_START`, `KH_UNI_KMERS`, `KH_UNI_COUNT_SUM`, `KH_UNI_FLAGS`.
+pub const UNI_WORDS: usize = 4;
+pub const UNI_START: usize = 0;
+pub const UNI_KMERS: usize = 1;
+pub const UNI_COUNT_SUM: usize = 2;
+pub const UNI_FLAGS: usize = 3;
+/// `KH_UNI_CIRCULAR`: bit 0 of the flags word -- the chain closes, and the closing overlap is not repeated in the bases.
+pub const UNI_CIRCULAR: u64 = 1;
 
 /// KH_SET_*: the set operation of `kh_combine_into`.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -484,6 +497,23 @@ impl HipKmerMap {
         let mut m = vec![0u8; keys.len()];
         check(self.ctx, unsafe { sys::kh_graph_masks(self.ctx, keys.as_ptr(), keys.len() as u64, min_count, m.as_mut_ptr()) })?;
         Ok(m)
+    }
+
+    /// The unitigs of this table's de Bruijn graph (`kh_unitigs_begin` / `kh_unitigs_copy` / `kh_unitigs_end`), built on the
+    /// device over the node set S = the keys with a count of at least `max(min_count, 1)`: [`UNI_WORDS`] words per unitig
+    /// (its first base's offset, its k-mers L, the sum of their counts, the flags) and the bases (ASCII, unitig after unitig; a
+    /// unitig has L + k - 1 of them), in ascending key order of the unitigs' first nodes.  The same table content gives the same
+    /// bytes whatever the table's geometry.
+    pub fn unitigs(&self, min_count: u64) -> Result<(Vec<u64>, Vec<u8>), HipError> {
+        let (mut nu, mut nb) = (0u64, 0u64);
+        check(self.ctx, unsafe { sys::kh_unitigs_begin(self.ctx, min_count, &mut nu, &mut nb) })?;
+        let mut rows = vec![0u64; nu as usize * UNI_WORDS];
+        let mut bases = vec![0u8; nb as usize];
+        let rc = unsafe { sys::kh_unitigs_copy(self.ctx, rows.as_mut_ptr(), nu, bases.as_mut_ptr(), nb) };
+        let end = unsafe { sys::kh_unitigs_end(self.ctx) };
+        check(self.ctx, rc)?;
+        check(self.ctx, end)?;
+        Ok((rows, bases))
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

@@ -400,6 +400,49 @@ int kh_graph_stats(kh_ctx *ctx, uint64_t min_count, uint64_t *out /* KH_GRAPH_WO
 int kh_graph_masks_device(kh_ctx *ctx, const uint64_t *d_keys, uint64_t n, uint64_t min_count, uint8_t *d_masks);
 int kh_graph_masks(kh_ctx *ctx, const uint64_t *keys, uint64_t n, uint64_t min_count, uint8_t *masks);
 
+/* ---- unitigs of a count table: the compacted de Bruijn graph (no reference counterpart) --- */
+/* The maximal non-branching paths of the node-centric de Bruijn graph of S -- what BCALM or Cuttlefish build after KMC --,
+ * built on the device.  Everything follows from k, min_count and the table's counts; the table's size, geometry and form do
+ * not show in the result.
+ * NODE SET S: as for kh_graph_*, the canonical keys with a count of at least max(min_count, 1).
+ * ORIENTED NODE: (x, +) spells x's canonical string s, (x, -) spells rc(s).  rev() flips the sign.
+ * SUCCESSORS of an oriented node u that spells w: for each letter c, the string t = w[1:] + c gives a successor if canon(t) = y
+ *   is in S; that successor is (y, +) if t equals y's string, else (y, -).  The out-degree of (x, +) is popcount(mask & 15), of
+ *   (x, -) popcount(mask >> 4), with the mask of kh_graph_*.  The in-degree of v is the out-degree of rev(v): u -> v holds iff
+ *   rev(v) -> rev(u).
+ * COMPACTABLE LINK u -> v: outdeg(u) = 1, outdeg(rev(v)) = 1, node(u) != node(v) (which excludes the homopolymer loop u -> u
+ *   and the hairpin u -> rev(u)), and neither node is a palindrome (a string equal to its reverse complement: even k only).  A
+ *   palindrome takes part in no link and is always a unitig of its own.
+ * UNITIG: a maximal chain u1 -> ... -> uL of compactable links.  Its sequence is spell(u1) followed by the last letter of each
+ *   further ui: L + k - 1 bases.  A chain never meets its own mirror image, so every node of S lies in exactly one unitig, read
+ *   in one of two mirrored directions.
+ * WHICH READING is reported.  L = 1: (x, +).  A chain that does not close: the reading whose first node has the smaller key of
+ *   the two end nodes.  A chain that closes (uL -> u1 is compactable too): the reading that contains (m, +) for the smallest key
+ *   m of the cycle, starting there; its KH_UNI_CIRCULAR flag is set and the closing overlap is not repeated in the bases.
+ * ORDER: unitigs come in ascending key order of their first node.  The same table content gives the same bytes on every run
+ *   and for every geometry and form (the rule of kh_result_sorted).
+ * kh_unitigs_begin builds the rows (KH_UNI_WORDS words per unitig) and the bases (ASCII ACGT, unitig after unitig, no
+ * separators: START of row i + 1 = START + KMERS + k - 1 of row i) into device memory that the context owns until
+ * kh_unitigs_end, the next kh_unitigs_begin, kh_reset or kh_destroy.  It enters like kh_result_sorted_device: pending pushes
+ * are counted first, the table is read in the form it is in (kh_stats stays what it was), a kh_result_text_* stream in progress
+ * ends; scratch comes from the idle partition buffers where there are any.  No memory is KH_ERR_OOM with nothing allocated and
+ * the context usable; a shard is KH_ERR_STATE as for kh_graph_*; node ids are 32-bit, and more than 2^31 - 1 nodes is
+ * KH_ERR_RANGE.  An empty S is 0 unitigs and 0 bases.
+ * The copies check the capacities first: row_cap < n_unitigs or base_cap < n_bases is KH_ERR_RANGE and NOTHING is written to
+ * either array; a NULL array with capacity 0 skips that array.  A copy without a live begin -- none yet, or any call since that
+ * entered the context as a writer (what ends a text stream) -- is KH_ERR_STATE.  The readers kh_result_size, kh_lookup,
+ * kh_histogram, kh_graph_* and kh_profile* may come between.  kh_unitigs_end with nothing begun is KH_OK. */
+#define KH_UNI_WORDS 4        /* uint64 words per unitig row */
+#define KH_UNI_START 0        /* offset of its first base in the base array */
+#define KH_UNI_KMERS 1        /* L; it has L + k - 1 bases */
+#define KH_UNI_COUNT_SUM 2    /* sum of its k-mers' counts, modulo 2^64 */
+#define KH_UNI_FLAGS 3        /* bit 0: KH_UNI_CIRCULAR */
+#define KH_UNI_CIRCULAR 1
+int kh_unitigs_begin(kh_ctx *ctx, uint64_t min_count, uint64_t *n_unitigs, uint64_t *n_bases);
+int kh_unitigs_copy_device(kh_ctx *ctx, uint64_t *d_rows, uint64_t row_cap, uint8_t *d_bases, uint64_t base_cap);
+int kh_unitigs_copy(kh_ctx *ctx, uint64_t *rows, uint64_t row_cap, uint8_t *bases, uint64_t base_cap);
+int kh_unitigs_end(kh_ctx *ctx);
+
 /* ---- multi-GPU merge (no reference counterpart) ----------- */
 /* Owner shard of a packed canonical k-mer among nparts shards: a fast-range of the top bits of
  * the table hash, so a shard is a contiguous range of table regions (same function on host and

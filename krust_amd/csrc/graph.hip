@@ -15,25 +15,7 @@
 
 namespace kh {
 
-// The mask of key x: eight canonical neighbour keys from ONE reverse complement, eight ref() (eight Feistel hashes), the eight
-// first-slot loads all in flight before the first is looked at -- as profile_kernel and join_kernel keep eight loads of eight
-// windows / slots in flight --, then the eight walks.  A neighbour is in the node set iff its count is >= min_count (>= 1).
-template <typename PRB>
-__device__ __forceinline__ uint32_t graph_mask_of(const PRB &prb, u64 x, uint32_t k, u64 min_count) {
-    uint64_t nb[8];
-    kh_graph_neighbours(x, k, nb);
-    typename PRB::Ref ref[8];
-    typename PRB::Word first[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ref[j] = prb.ref(nb[j]);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) first[j] = PRB::load(ref[j]);
-    uint32_t mask = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        if (PRB::resolve64(ref[j], first[j]) >= min_count) mask |= 1u << j;
-    return mask;
-}
+// graph_mask_of(prb, x, k, min_count), the mask of one key, is in probe.hip.h: unitig.hip asks it too.
 
 // ---- the caller's keys as a source: any alignment -----------------------------------------------------------------------------
 struct GsKeys {

@@ -46,6 +46,7 @@ void read_knobs(Knobs &k) {
 int enter(kh_ctx *c, bool flush_pending, bool need_table, bool keep_window, bool narrow_ok, bool reader) {
     if (!c) return KH_ERR_BAD_ARG;
     if (!reader) c->ts.on = false;  // (whatever may change the table, or takes the partition buffers, ends a text stream)
+    if (!reader) c->un.live = false;  // (... and makes the unitigs of kh_unitigs_begin stale: their copies refuse)
 #if KH_TESTING
     read_knobs(c->knobs);  // (tests flip the switches between calls on one context; the product library reads them once, at kh_create)
 #endif
@@ -537,6 +538,7 @@ extern "C" void kh_destroy(kh_ctx *c) {
     text_release(c);
     if (c->cstream2) (void)hipStreamSynchronize(c->cstream2);
     profile_release(c);
+    unitigs_release(c);
     for (int i = 0; i < 2; ++i) {
         if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
         if (c->acc[i]) (void)hipFree(c->acc[i]);
@@ -586,6 +588,7 @@ extern "C" int kh_reset(kh_ctx *c) {
     c->txt_unscanned.on = false;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     drain_events(c);
+    unitigs_release(c);
     // Lazy: no table_init here (5.5 ms for a 34 GB table).  A partitioned batch into an empty table
     // rewrites every region; any other use clears first (clear_if_dirty).
     if (!c->table_empty) c->table_dirty = true;

@@ -1,7 +1,8 @@
 // probe.hip.h -- a read-only probe of one table, in either of its forms: what profile.hip asks per window of new sequences
-// and join.hip per live slot of another table, and graph.hip eight times per k-mer of the same table.
+// and join.hip per live slot of another table, and graph.hip and unitig.hip eight times per k-mer of the same table.
 #pragma once
 #include "ctx.hip.h"
+#include "graph_bits.h"
 
 namespace kh {
 
@@ -56,6 +57,18 @@ struct PfWide {
         }
         return 0ull;
     }
+    // the same walk for WHERE the key is: its slot index in the table (what JsWide::load takes), ~0 when it is absent (unitig.hip)
+    __device__ __forceinline__ u64 resolve_slot(const Ref &r, Word w) const {
+        uint32_t off = r.off;
+        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
+            const u64 sk = ((u64)w.y << 32) | w.x;
+            if (sk == r.key) return (u64)(r.reg - tg.table) + off;
+            if (sk == KH_EMPTY_KEY) return ~0ull;
+            off = (off + 1) & REGION_MASK;
+            w = *reinterpret_cast<const uint4 *>(&r.reg[off]);
+        }
+        return ~0ull;
+    }
 };
 
 struct PfNarrow {
@@ -100,7 +113,38 @@ struct PfNarrow {
         }
         return 0ull;
     }
+    __device__ __forceinline__ u64 resolve_slot(const Ref &r, Word w) const {  // (the slot index JsNarrow::load takes)
+        uint32_t off = r.off;
+        for (uint32_t probes = 0; probes < REGION_SLOTS; ++probes) {
+            if ((w >> 32) == 0) return ~0ull;
+            if ((uint32_t)w == r.pay) return (u64)(r.reg - ntab) + off;
+            off = (off + 1) & REGION_MASK;
+            w = r.reg[off];
+        }
+        return ~0ull;
+    }
 };
+
+// The de Bruijn mask of key x (include/kmerhip.h, kh_graph_*): eight canonical neighbour keys from ONE reverse complement, eight
+// ref() (eight Feistel hashes), the eight first-slot loads all in flight before the first is looked at -- as profile_kernel and
+// join_kernel keep eight loads of eight windows / slots in flight --, then the eight walks.  A neighbour is in the node set iff
+// its count is >= min_count (>= 1).  (graph.hip per key; unitig.hip per node, once.)
+template <typename PRB>
+__device__ __forceinline__ uint32_t graph_mask_of(const PRB &prb, u64 x, uint32_t k, u64 min_count) {
+    uint64_t nb[8];
+    kh_graph_neighbours(x, k, nb);
+    typename PRB::Ref ref[8];
+    typename PRB::Word first[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ref[j] = prb.ref(nb[j]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) first[j] = PRB::load(ref[j]);
+    uint32_t mask = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (PRB::resolve64(ref[j], first[j]) >= min_count) mask |= 1u << j;
+    return mask;
+}
 
 // ---- source views: slot i of a scanned table -> (key, count), false for a free slot (join.hip, graph.hip) -------------------
 struct JsWide {

@@ -1,0 +1,498 @@
+// unitig.hip -- kh_unitigs_*: the unitigs (maximal non-branching paths) of the de Bruijn graph of a count table, built on the
+// device (what BCALM / Cuttlefish build after KMC).  No reference counterpart.  The definitions are in include/kmerhip.h, the
+// argument that a chain never meets its own mirror image in DESIGN.md 4.11.
+//
+// Nodes are the table's pairs in ascending key order (compact_pairs + the radix sort of sort.hip): node id = rank, so "smaller key"
+// is "smaller id" and unitigs come out in id order of their first nodes without a second sort.  An oriented node is the state
+// 2 * id + sign (unitig_bits.h).
+//   unitig_index_kernel<PRB>   per node: its slot in the table -> slot2id[slot] = id (resolve_slot, probe.hip.h), and its mask
+//                              (graph_mask_of) -> masks[id]
+//   unitig_link_kernel<PRB>    per node, both signs: the single successor where the out-degree is 1, its id by ONE probe, the four
+//                              conditions of a compactable link -> next[state] or KH_UNI_NONE
+//   unitig_rank_init_kernel,   chain ranking by pointer doubling over the 2n states: (state reached, hops so far, smallest node id
+//   unitig_rank_round_kernel   seen), one launch per round, double-buffered, a "something changed" word read back per round; the
+//                              host bounds the rounds by ceil(log2(2n)) + 1
+//   unitig_cut_kernel          states that have not reached an end by then lie on cycles and know their cycle's smallest id m: the
+//                              link into (m, +) and its mirror out of (m, -) go, m is marked circular, and the ranking runs again
+//   unitig_reading_kernel      per node, from the two ranks of (x, +) and (x, -): its unitig's first node, its own sign in the
+//                              reported reading, its position; first nodes are flagged
+//   device_scan                flags -> unitig index; then L + k - 1 per unitig -> START
+//   unitig_row_kernel          per first node: KMERS, FLAGS, the length
+//   unitig_place_kernel        per node: its id and sign into unitig order (4-byte stores); START
+//   unitig_sum_kernel          COUNT_SUM: a segmented sum over that order -- one atomic per (wave, unitig), never one per node
+//   unitig_bases_kernel        per 16 bytes of the base array: the letters, one aligned 16-byte store (bytes only in the array's tail)
+// No kernel waits for another workgroup, and no device loop is without a bound.  Rates were not measured (profiles/README.md r13).
+#include "ctx.hip.h"
+#include "probe.hip.h"
+#include "unitig_bits.h"
+
+namespace kh {
+
+struct UniRank {  // 2n entries each
+    uint32_t *tgt;   // the state reached so far (itself for an end: a state with no link out)
+    uint32_t *hops;  // links followed to get there
+    uint32_t *mn;    // smallest node id among the states from this one up to, not including, tgt
+};
+constexpr uint32_t UNI_SIGN = 0x80000000u;
+
+// kernel-resource-usage (gfx950, hipcc -O3), PfNarrow / PfWide: 65 / 96 VGPRs (eight probes in flight, as graph_kernel), 68 / 63 SGPRs, no LDS,
+// no scratch, no spills, 7 / 5 waves per SIMD.
+template <typename PRB>
+__global__ __launch_bounds__(BLOCK) void unitig_index_kernel(const u64 *__restrict__ keys, uint32_t n, uint32_t k, u64 min_count, PRB prb, u64 cap,
+                                                             uint32_t *__restrict__ slot2id, uint8_t *__restrict__ masks) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        const u64 x = keys[i];
+        const typename PRB::Ref ref = prb.ref(x);
+        const typename PRB::Word w = PRB::load(ref);
+        const uint32_t mask = graph_mask_of(prb, x, k, min_count);
+        const u64 slot = prb.resolve_slot(ref, w);
+        if (slot < cap) slot2id[slot] = (uint32_t)i;  // (always: x came out of this table)
+        masks[i] = (uint8_t)mask;
+    }
+}
+
+// kernel-resource-usage (gfx950, hipcc -O3), PfNarrow / PfWide: 29 / 39 VGPRs, 66 / 61 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+template <typename PRB>
+__global__ __launch_bounds__(BLOCK) void unitig_link_kernel(const u64 *__restrict__ keys, uint32_t n, uint32_t k, PRB prb, u64 cap,
+                                                            const uint32_t *__restrict__ slot2id, const uint8_t *__restrict__ masks,
+                                                            uint32_t *__restrict__ next) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        const u64 x = keys[i];
+        const uint32_t mask = masks[i];
+        const bool pal = kh_unitig_palindrome(x, k);
+        u64 y[2];
+        uint32_t ys[2];
+        bool want[2];
+#pragma unroll
+        for (uint32_t sg = 0; sg < 2; ++sg) {
+            const uint32_t bits = kh_unitig_out_bits(mask, sg);
+            y[sg] = x;  // (a key that is there: the probe below needs no branch)
+            ys[sg] = 0;
+            want[sg] = !pal && __builtin_popcount(bits) == 1;
+            if (want[sg]) {
+                uint64_t yy;
+                uint32_t s;
+                bool yp;
+                kh_unitig_successor(x, k, sg, kh_unitig_letter_of_bit((uint32_t)__builtin_ctz(bits), sg), &yy, &s, &yp);
+                want[sg] = !kh_unitig_self_link(x, yy) && !yp;
+                if (want[sg]) {
+                    y[sg] = yy;
+                    ys[sg] = s;
+                }
+            }
+        }
+        typename PRB::Ref ref[2];
+        typename PRB::Word first[2];
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg) ref[sg] = prb.ref(y[sg]);
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg) first[sg] = PRB::load(ref[sg]);  // (both first-slot loads in flight)
+        uint32_t nx[2];
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg) {
+            nx[sg] = KH_UNI_NONE;
+            const u64 slot = prb.resolve_slot(ref[sg], first[sg]);
+            if (want[sg] && slot < cap) {
+                const uint32_t yid = slot2id[slot];
+                if (yid < n && __builtin_popcount(kh_unitig_out_bits(masks[yid], ys[sg] ^ 1u)) == 1) nx[sg] = 2u * yid + ys[sg];
+            }
+        }
+        *reinterpret_cast<uint2 *>(&next[2 * i]) = make_uint2(nx[0], nx[1]);
+    }
+}
+
+// kernel-resource-usage (gfx950, hipcc -O3): 12 VGPRs, 22 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void unitig_rank_init_kernel(const uint32_t *__restrict__ next, u64 states, UniRank r) {
+    for (u64 s = (u64)blockIdx.x * BLOCK + threadIdx.x; s < states; s += (u64)gridDim.x * BLOCK) {
+        const uint32_t nx = next[s];
+        r.tgt[s] = nx == KH_UNI_NONE ? (uint32_t)s : nx;
+        r.hops[s] = nx == KH_UNI_NONE ? 0u : 1u;
+        r.mn[s] = (uint32_t)(s >> 1);
+    }
+}
+
+// One round of pointer doubling: a state whose target is not an end takes over the target's jump.  (An end is told by next[], not
+// by tgt[t] == t: on a cycle whose length divides the hops so far a state's target is the state itself.)
+// kernel-resource-usage (gfx950, hipcc -O3): 13 VGPRs, 50 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void unitig_rank_round_kernel(const uint32_t *__restrict__ next, u64 states, UniRank a, UniRank b,
+                                                                  uint32_t *__restrict__ changed) {
+    bool any = false;
+    for (u64 s = (u64)blockIdx.x * BLOCK + threadIdx.x; s < states; s += (u64)gridDim.x * BLOCK) {
+        uint32_t t = a.tgt[s], h = a.hops[s], m = a.mn[s];
+        if (t < states && next[t] != KH_UNI_NONE) {
+            h += a.hops[t];  // (wraps on a cycle only, where it is not used)
+            const uint32_t mt = a.mn[t];
+            m = mt < m ? mt : m;
+            t = a.tgt[t];
+            any = true;
+        }
+        b.tgt[s] = t;
+        b.hops[s] = h;
+        b.mn[s] = m;
+    }
+    if (kh_any(any) && lane_id() == 0) *changed = 1u;  // (every writer writes the same word)
+}
+
+// After the last round: (m, +) with an unfinished target and m the smallest id of its cycle.  The cycle through (m, +) loses the
+// link into (m, +) -- its predecessor is rev(next((m, -))) --, the mirrored cycle the link out of (m, -).  Only this lane writes to
+// either cycle, and it has read before it writes.
+// kernel-resource-usage (gfx950, hipcc -O3): 14 VGPRs, 30 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void unitig_cut_kernel(uint32_t *__restrict__ next, uint32_t n, UniRank r, uint8_t *__restrict__ circ) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        const uint32_t t = r.tgt[2 * i];
+        if (r.mn[2 * i] != (uint32_t)i || t >= 2ull * n || next[t] == KH_UNI_NONE) continue;
+        const uint32_t back = next[2 * i + 1];  // (never NONE: the mirrored cycle passes through (m, -))
+        if (back == KH_UNI_NONE || back >= 2ull * n) continue;
+        next[back ^ 1u] = KH_UNI_NONE;
+        next[2 * i + 1] = KH_UNI_NONE;
+        circ[i] = 1;
+    }
+}
+
+// With E+ = (b, .) the end reached from (x, +) after d+ links and E- = (a, .) the end reached from (x, -) after d-: the chain read
+// with x as + starts at rev(E-), has x at position d- and ends in E+; the two end nodes are a and b, and L = d+ + d- + 1.
+// kernel-resource-usage (gfx950, hipcc -O3): 16 VGPRs, 50 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void unitig_reading_kernel(const uint32_t *__restrict__ next, uint32_t n, UniRank r, uint32_t *__restrict__ head,
+                                                               uint32_t *__restrict__ posg, uint32_t *__restrict__ first, uint32_t *__restrict__ err) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        const uint32_t ep = r.tgt[2 * i], dp = r.hops[2 * i], em = r.tgt[2 * i + 1], dm = r.hops[2 * i + 1];
+        uint32_t h = (uint32_t)i, p = 0;
+        if (ep >= 2ull * n || em >= 2ull * n || next[ep] != KH_UNI_NONE || next[em] != KH_UNI_NONE) {
+            *err = 1u;  // (a chain that did not end: never, behind the cut)
+        } else {
+            const uint32_t a = em >> 1, b = ep >> 1;
+            if (a < b) {
+                h = a;
+                p = dm;
+            } else if (b < a) {
+                h = b;
+                p = dp | UNI_SIGN;
+            } else if (dp | dm) {
+                *err = 1u;  // (both ends in one node: L = 1)
+            }
+        }
+        head[i] = h;
+        posg[i] = p;
+        first[i] = h == (uint32_t)i ? 1u : 0u;
+    }
+}
+
+// kernel-resource-usage (gfx950, hipcc -O3): 18 VGPRs, 34 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void unitig_row_kernel(uint32_t n, uint32_t k, UniRank r, const uint32_t *__restrict__ first,
+                                                           const u64 *__restrict__ uidx, const uint8_t *__restrict__ circ, u64 nu,
+                                                           uint32_t *__restrict__ ulen, u64 *__restrict__ rows) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        if (!first[i]) continue;
+        const u64 u = uidx[i];
+        if (u >= nu) continue;  // (never)
+        const uint32_t L = r.hops[2 * i] + r.hops[2 * i + 1] + 1u;
+        ulen[u] = L + k - 1u;
+        rows[KH_UNI_WORDS * u + KH_UNI_KMERS] = L;
+        rows[KH_UNI_WORDS * u + KH_UNI_COUNT_SUM] = 0;
+        rows[KH_UNI_WORDS * u + KH_UNI_FLAGS] = circ[i] ? KH_UNI_CIRCULAR : 0;
+    }
+}
+
+// Node q of the order array is the q-th k-mer of the base array's unitigs: unitig u's nodes start at ustart[u] - u (k - 1).
+// kernel-resource-usage (gfx950, hipcc -O3): 18 VGPRs, 41 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void unitig_place_kernel(uint32_t n, uint32_t k, const uint32_t *__restrict__ head, const uint32_t *__restrict__ posg,
+                                                             const u64 *__restrict__ uidx, const u64 *__restrict__ ustart, u64 nu,
+                                                             uint32_t *__restrict__ order, uint32_t *__restrict__ ordu, u64 *__restrict__ rows,
+                                                             uint32_t *__restrict__ err) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        const uint32_t h = head[i], pg = posg[i];
+        const u64 u = h < n ? uidx[h] : nu;
+        if (u >= nu) {
+            *err = 1u;
+            continue;
+        }
+        const u64 st = ustart[u];
+        const u64 q = st - u * (k - 1u) + (pg & ~UNI_SIGN);
+        if (q >= n) {
+            *err = 1u;
+            continue;
+        }
+        order[q] = (uint32_t)i | (pg & UNI_SIGN);
+        ordu[q] = (uint32_t)u;
+        if (h == (uint32_t)i) rows[KH_UNI_WORDS * u + KH_UNI_START] = st;
+    }
+}
+
+// COUNT_SUM: lanes of a wave that hold nodes of one unitig are neighbours; a segmented scan over the wave (six shuffle steps),
+// then the last lane of every run adds the run's sum to its row -- one atomic per (wave, unitig).
+// kernel-resource-usage (gfx950, hipcc -O3): 21 VGPRs, 46 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void unitig_sum_kernel(uint32_t n, const uint32_t *__restrict__ order, const uint32_t *__restrict__ ordu,
+                                                           const u64 *__restrict__ counts, u64 nu, u64 *__restrict__ rows) {
+    const uint32_t lane = lane_id();
+    for (u64 base = (u64)blockIdx.x * BLOCK; base < n; base += (u64)gridDim.x * BLOCK) {  // (uniform: every lane shuffles)
+        const u64 q = base + threadIdx.x;
+        uint32_t u = 0xFFFFFFFFu;
+        u64 v = 0;
+        if (q < n) {
+            u = ordu[q];
+            const uint32_t id = order[q] & ~UNI_SIGN;
+            v = id < n ? counts[id] : 0;
+        }
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const u64 vu = __shfl_up(v, d, 64);
+            const uint32_t uu = (uint32_t)__shfl_up((int)u, d, 64);
+            if (lane >= d && uu == u) v += vu;
+        }
+        const uint32_t un = (uint32_t)__shfl_down((int)u, 1, 64);
+        if (q < n && u < nu && (lane == 63 || un != u))
+            (void)__hip_atomic_fetch_add(&rows[KH_UNI_WORDS * (u64)u + KH_UNI_COUNT_SUM], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// Bytes [16 g, 16 g + 16) of the base array.  The unitig of the first byte by bisection of ustart (nu + 1 entries), the following
+// ones by stepping on.  Byte o of unitig u: o < k - 1 is letter o of its first node, else the LAST letter of node o - (k - 1).
+// kernel-resource-usage (gfx950, hipcc -O3): 28 VGPRs, 59 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void unitig_bases_kernel(const u64 *__restrict__ keys, uint32_t n, uint32_t k, const uint32_t *__restrict__ order,
+                                                             const u64 *__restrict__ ustart, u64 nu, u64 nbases, uint8_t *__restrict__ bases) {
+    const u64 ngroups = (nbases + 15) / 16;
+    for (u64 g = (u64)blockIdx.x * BLOCK + threadIdx.x; g < ngroups; g += (u64)gridDim.x * BLOCK) {
+        const u64 b0 = 16 * g;
+        u64 lo = 0, hi = nu;
+        for (int it = 0; it < 64 && hi - lo > 1; ++it) {
+            const u64 mid = lo + (hi - lo) / 2;
+            if (ustart[mid] <= b0) lo = mid;
+            else hi = mid;
+        }
+        u64 u = lo, ust = ustart[u], unext = ustart[u + 1];
+        u64 lastq = ~0ull, w = 0;
+        uint32_t word[4] = {0, 0, 0, 0};
+#pragma unroll 1
+        for (uint32_t j = 0; j < 16; ++j) {
+            const u64 b = b0 + j;
+            if (b >= nbases) break;
+            for (int a = 0; a < 17 && b >= unext && u + 1 < nu; ++a) {  // (a unitig has at least one byte)
+                ++u;
+                ust = unext;
+                unext = ustart[u + 1];
+            }
+            const u64 o = b - ust, ns = ust - u * (k - 1u);
+            u64 q = o < k - 1u ? ns : ns + o - (k - 1u);
+            const uint32_t li = o < k - 1u ? (uint32_t)o : k - 1u;
+            if (q >= n) q = n - 1;  // (never: a guard, not a path)
+            if (q != lastq) {
+                const uint32_t rec = order[q];
+                const uint32_t id = rec & ~UNI_SIGN;
+                w = kh_unitig_spell(keys[id < n ? id : 0], k, rec >> 31);
+                lastq = q;
+            }
+            word[j >> 2] |= (uint32_t)kh_unitig_letter(w, k, li) << (8u * (j & 3u));
+        }
+        if (b0 + 16 <= nbases) {
+            *reinterpret_cast<uint4 *>(bases + b0) = make_uint4(word[0], word[1], word[2], word[3]);
+        } else {  // the cut group at the end of the array
+            for (uint32_t j = 0; j < 16 && b0 + j < nbases; ++j) bases[b0 + j] = (uint8_t)(word[j >> 2] >> (8u * (j & 3u)));
+        }
+    }
+}
+
+}  // namespace kh
+
+namespace khi {
+
+void unitigs_release(kh_ctx *c) {
+    if (c->un.rows) (void)hipFree(c->un.rows);  // (synchronises the device)
+    if (c->un.bases) (void)hipFree(c->un.bases);
+    c->un = kh_ctx::Unitigs();
+}
+
+namespace {
+
+int soft_oom(kh_ctx *c, const char *what) {  // (not fail(): an allocation of this call alone failed, the table is untouched)
+    c->last_error = what;
+    return KH_ERR_OOM;
+}
+
+unsigned uni_grid(u64 items) { return (unsigned)grid_for(items); }
+
+// The chain ranking over `states` states: init into *cur, then rounds that ping-pong between *cur and *oth until nothing changes
+// or the bound is reached.  *open = the last round still changed something: states on cycles.
+int unitig_rank(kh_ctx *c, const uint32_t *next, u64 states, kh::UniRank *cur, kh::UniRank *oth, uint32_t *d_flag, bool *open) {
+    hipLaunchKernelGGL(kh::unitig_rank_init_kernel, dim3(uni_grid(states)), dim3(kh::BLOCK), 0, c->stream, next, states, *cur);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t rounds = 1;  // ceil(log2(states)) + 1
+    while ((1ull << (rounds - 1)) < states) ++rounds;
+    *open = true;
+    for (uint32_t r = 0; r < rounds; ++r) {
+        HIP_TRY(c, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(kh::unitig_rank_round_kernel, dim3(uni_grid(states)), dim3(kh::BLOCK), 0, c->stream, next, states, *cur, *oth, d_flag);
+        HIP_TRY(c, hipGetLastError());
+        uint32_t changed = 0;
+        HIP_TRY(c, hipMemcpyAsync(&changed, d_flag, sizeof(changed), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::swap(*cur, *oth);
+        if (!changed) {
+            *open = false;
+            break;
+        }
+    }
+    return KH_OK;
+}
+
+int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc) {
+    const uint32_t n32 = (uint32_t)n, k = c->k;
+    const u64 states = 2 * n;
+    u64 *const keys = (u64 *)sc.take(n * sizeof(u64));
+    u64 *const counts = (u64 *)sc.take(n * sizeof(u64));
+    if (!keys || !counts) return soft_oom(c, "device memory for the unitigs' nodes");
+    int rc = sorted_into(c, keys, counts, n, mc, sc);
+    if (rc != KH_OK) return rc;
+    uint32_t *const slot2id = (uint32_t *)sc.take(c->cap * sizeof(uint32_t));
+    uint8_t *const masks = (uint8_t *)sc.take(n);
+    uint8_t *const circ = (uint8_t *)sc.take(n);
+    uint32_t *const next = (uint32_t *)sc.take(states * sizeof(uint32_t));
+    uint32_t *const rank = (uint32_t *)sc.take(6 * states * sizeof(uint32_t));
+    u64 *const uidx = (u64 *)sc.take((n + 1) * sizeof(u64));
+    uint32_t *const d_flag = (uint32_t *)sc.take(2 * sizeof(uint32_t));  // "something changed", "something is inconsistent"
+    if (!slot2id || !masks || !circ || !next || !rank || !uidx || !d_flag) return soft_oom(c, "device memory for the unitigs' scratch");
+    kh::UniRank cur{rank, rank + states, rank + 2 * states}, oth{rank + 3 * states, rank + 4 * states, rank + 5 * states};
+    HIP_TRY(c, hipMemsetAsync(slot2id, 0xFF, c->cap * sizeof(uint32_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(circ, 0, n, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_flag, 0, 2 * sizeof(uint32_t), c->stream));
+    if (c->narrow) {
+        const kh::PfNarrow prb{(const u64 *)c->ntab, c->narrow_g};
+        hipLaunchKernelGGL((kh::unitig_index_kernel<kh::PfNarrow>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, mc, prb,
+                           c->cap, slot2id, masks);
+        hipLaunchKernelGGL((kh::unitig_link_kernel<kh::PfNarrow>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, prb,
+                           c->cap, (const uint32_t *)slot2id, (const uint8_t *)masks, next);
+    } else {
+        const kh::PfWide prb{table_geom(c, c->table, c->cap)};
+        hipLaunchKernelGGL((kh::unitig_index_kernel<kh::PfWide>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, mc, prb,
+                           c->cap, slot2id, masks);
+        hipLaunchKernelGGL((kh::unitig_link_kernel<kh::PfWide>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, prb,
+                           c->cap, (const uint32_t *)slot2id, (const uint8_t *)masks, next);
+    }
+    HIP_TRY(c, hipGetLastError());
+
+    bool open = false;
+    if ((rc = unitig_rank(c, next, states, &cur, &oth, d_flag, &open)) != KH_OK) return rc;
+    if (open) {  // cycles: cut each at its smallest node and rank again
+        hipLaunchKernelGGL(kh::unitig_cut_kernel, dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, next, n32, cur, circ);
+        HIP_TRY(c, hipGetLastError());
+        if ((rc = unitig_rank(c, next, states, &cur, &oth, d_flag, &open)) != KH_OK) return rc;
+        if (open) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: a chain is still closed behind the cut (internal error)");
+    }
+
+    // the other rank buffer is free from here on: five arrays of n words live in it
+    uint32_t *const head = oth.tgt, *const order = oth.tgt + n, *const posg = oth.hops, *const ordu = oth.hops + n, *const first = oth.mn;
+    hipLaunchKernelGGL(kh::unitig_reading_kernel, dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const uint32_t *)next, n32, cur, head, posg, first,
+                       d_flag + 1);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = device_scan(c, first, n, uidx)) != KH_OK) return rc;
+    u64 nu = 0;
+    HIP_TRY(c, hipMemcpyAsync(&nu, uidx + n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (nu == 0 || nu > n) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: the first nodes do not add up (internal error)");
+
+    uint32_t *const ulen = (uint32_t *)sc.take(nu * sizeof(uint32_t));
+    u64 *const ustart = (u64 *)sc.take((nu + 1) * sizeof(u64));
+    if (!ulen || !ustart) return soft_oom(c, "device memory for the unitigs' offsets");
+    if (hipMalloc((void **)&c->un.rows, nu * KH_UNI_WORDS * sizeof(u64)) != hipSuccess) {
+        (void)hipGetLastError();
+        c->un.rows = nullptr;
+        return soft_oom(c, "hipMalloc(unitig rows)");
+    }
+    hipLaunchKernelGGL(kh::unitig_row_kernel, dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, n32, k, cur, (const uint32_t *)first, (const u64 *)uidx,
+                       (const uint8_t *)circ, nu, ulen, c->un.rows);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = device_scan(c, ulen, nu, ustart)) != KH_OK) return rc;
+    u64 nb = 0;
+    HIP_TRY(c, hipMemcpyAsync(&nb, ustart + nu, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (nb != n + nu * (k - 1)) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: the unitigs' lengths do not add up (internal error)");
+    if (hipMalloc((void **)&c->un.bases, nb) != hipSuccess) {
+        (void)hipGetLastError();
+        c->un.bases = nullptr;
+        return soft_oom(c, "hipMalloc(unitig bases)");
+    }
+    hipLaunchKernelGGL(kh::unitig_place_kernel, dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, n32, k, (const uint32_t *)head, (const uint32_t *)posg,
+                       (const u64 *)uidx, (const u64 *)ustart, nu, order, ordu, c->un.rows, d_flag + 1);
+    hipLaunchKernelGGL(kh::unitig_sum_kernel, dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, n32, (const uint32_t *)order, (const uint32_t *)ordu,
+                       (const u64 *)counts, nu, c->un.rows);
+    hipLaunchKernelGGL(kh::unitig_bases_kernel, dim3(uni_grid((nb + 15) / 16)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k,
+                       (const uint32_t *)order, (const u64 *)ustart, nu, nb, c->un.bases);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t bad = 0;
+    HIP_TRY(c, hipMemcpyAsync(&bad, d_flag + 1, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (bad) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: the chains are inconsistent (internal error)");
+    c->un.n_unitigs = nu;
+    c->un.n_bases = nb;
+    return KH_OK;
+}
+
+// What the two copies check before they write anything.
+int unitigs_copy_enter(kh_ctx *c, const char *who, const void *rows, u64 row_cap, const void *bases, u64 base_cap) {
+    if (!c) return KH_ERR_BAD_ARG;
+    int rc = enter(c, true, true, false, true, true);  // a reader
+    if (rc != KH_OK) return rc;
+    if (!c->un.live)
+        return fail(c, KH_ERR_STATE, (std::string(who) + ": no unitigs: kh_unitigs_begin first (anything that changes the table makes them stale)").c_str());
+    if ((row_cap && !rows) || (base_cap && !bases)) return fail(c, KH_ERR_BAD_ARG, (std::string(who) + ": NULL array").c_str());
+    if ((rows || row_cap) && row_cap < c->un.n_unitigs) return fail(c, KH_ERR_RANGE, (std::string(who) + ": row array too small").c_str());
+    if ((bases || base_cap) && base_cap < c->un.n_bases) return fail(c, KH_ERR_RANGE, (std::string(who) + ": base array too small").c_str());
+    return KH_OK;
+}
+
+}  // namespace
+}  // namespace khi
+using namespace khi;
+
+extern "C" int kh_unitigs_begin(kh_ctx *c, uint64_t min_count, uint64_t *n_unitigs, uint64_t *n_bases) {
+    if (!c) return KH_ERR_BAD_ARG;
+    if (!n_unitigs || !n_bases) return fail(c, KH_ERR_BAD_ARG, "kh_unitigs_begin: NULL output");
+    *n_unitigs = *n_bases = 0;
+    if (c->shard_shift) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: the table is a shard; its k-mers' neighbours live on other owners");
+    int rc = enter(c, true, true, false, true);  // as kh_result_sorted_device: the partition buffers are taken, a text stream ends
+    if (rc != KH_OK) return rc;
+    unitigs_release(c);
+    const u64 mc = min_count ? min_count : 1;
+    uint64_t n = 0;
+    if ((rc = kh_result_size(c, mc, &n)) != KH_OK) return rc;
+    if (n > 0x7FFFFFFFull) return fail(c, KH_ERR_RANGE, "kh_unitigs_begin: more than 2^31 - 1 nodes: node ids are 32-bit");
+    if (n) {
+        {
+            SortScratch sc(c);
+            rc = unitigs_build(c, n, mc, sc);
+            if (rc != KH_OK) (void)hipStreamSynchronize(c->stream);  // (before the scratch goes back)
+        }
+        if (rc != KH_OK) {
+            unitigs_release(c);
+            return rc;
+        }
+    }
+    c->un.live = true;
+    *n_unitigs = c->un.n_unitigs;
+    *n_bases = c->un.n_bases;
+    return KH_OK;
+}
+
+extern "C" int kh_unitigs_copy_device(kh_ctx *c, uint64_t *d_rows, uint64_t row_cap, uint8_t *d_bases, uint64_t base_cap) {
+    int rc = unitigs_copy_enter(c, "kh_unitigs_copy_device", d_rows, row_cap, d_bases, base_cap);
+    if (rc != KH_OK) return rc;
+    if (d_rows && c->un.n_unitigs)
+        HIP_TRY(c, hipMemcpyAsync(d_rows, c->un.rows, c->un.n_unitigs * KH_UNI_WORDS * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
+    if (d_bases && c->un.n_bases) HIP_TRY(c, hipMemcpyAsync(d_bases, c->un.bases, c->un.n_bases, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return KH_OK;
+}
+
+extern "C" int kh_unitigs_copy(kh_ctx *c, uint64_t *rows, uint64_t row_cap, uint8_t *bases, uint64_t base_cap) {
+    int rc = unitigs_copy_enter(c, "kh_unitigs_copy", rows, row_cap, bases, base_cap);
+    if (rc != KH_OK) return rc;
+    if (rows && c->un.n_unitigs) rc = d2h_staged(c, rows, c->un.rows, c->un.n_unitigs * KH_UNI_WORDS * sizeof(u64));
+    if (rc == KH_OK && bases && c->un.n_bases) rc = d2h_staged(c, bases, c->un.bases, c->un.n_bases);
+    return rc;
+}
+
+extern "C" int kh_unitigs_end(kh_ctx *c) {
+    if (!c) return KH_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    unitigs_release(c);
+    return KH_OK;
+}

@@ -1,0 +1,44 @@
+// unitig_bits.h -- the oriented-successor arithmetic of the unitig construction (include/kmerhip.h, "unitigs of a count table"),
+// shared by unitig.hip and by a plain host compiler (tests/unitig_bits_check.cpp compares it with string arithmetic for every k).
+//
+// An oriented node is (x, sign): sign 0 = (x, +) spells x's canonical string s, sign 1 = (x, -) spells rc(s).  As a state number it
+// is 2 * id + sign with id = the rank of x among the nodes, so rev() is ^ 1.
+// The successor by letter c of a node that spells w is t = w[1:] + c; it is entered as (canon(t), +) if t is the canonical string,
+// else as (canon(t), -).  Which bit of the kh_graph_* mask says that this successor exists:
+//   sign 0: t = s[1:] + c                       -> the right neighbour by c:      bit c
+//   sign 1: t = rc(s)[1:] + c = rc(c' + s[:-1]) -> the left neighbour by c' = 3-c: bit 4 + (3 - c)
+#pragma once
+#include "kmer_bits.h"
+
+#define KH_UNI_NONE 0xFFFFFFFFu  // no compactable link out of this state
+
+// A string equal to its reverse complement (even k only; x is canonical, so this is the tie of the canonical choice).
+KH_HD bool kh_unitig_palindrome(uint64_t x, uint32_t k) { return kh_revcomp(x, k) == x; }
+
+// The four mask bits of the successors of (x, sign): the out-degree is their popcount.
+KH_HD uint32_t kh_unitig_out_bits(uint32_t mask, uint32_t sign) { return sign ? (mask >> 4) & 15u : mask & 15u; }
+
+// The letter c that bit j of kh_unitig_out_bits stands for.
+KH_HD uint32_t kh_unitig_letter_of_bit(uint32_t j, uint32_t sign) { return sign ? 3u - j : j; }
+
+// What (x, sign) spells, packed.
+KH_HD uint64_t kh_unitig_spell(uint64_t x, uint32_t k, uint32_t sign) { return sign ? kh_revcomp(x, k) : x; }
+
+// The successor of (x, sign) by letter c: *y = its canonical key, *ysign = the sign it is entered with (0 when t is y's string:
+// a palindrome is entered as +), *ypal = whether it is a palindrome.
+KH_HD void kh_unitig_successor(uint64_t x, uint32_t k, uint32_t sign, uint32_t c, uint64_t *y, uint32_t *ysign, bool *ypal) {
+    const uint64_t w = kh_unitig_spell(x, k, sign);
+    const uint64_t t = ((w << 2) | c) & kh_kmask(k);
+    const uint64_t rt = kh_revcomp(t, k);
+    *y = t < rt ? t : rt;
+    *ysign = t > rt ? 1u : 0u;
+    *ypal = t == rt;
+}
+
+// A link between a node and itself is never compacted: the homopolymer loop u -> u and the hairpin u -> rev(u).
+KH_HD bool kh_unitig_self_link(uint64_t x, uint64_t y) { return x == y; }
+
+// The ASCII letter at position i (0 = first) of a packed k-letter string.
+KH_HD uint8_t kh_unitig_letter(uint64_t w, uint32_t k, uint32_t i) {
+    return (uint8_t)((0x54474341u >> (8u * (uint32_t)((w >> (2u * (k - 1u - i))) & 3u))) & 0xFFu);  // "ACGT"
+}

@@ -28,6 +28,7 @@ static const char *USAGE =
     "       kmerust combine <intersect|union|subtract|count-subtract> <INDEX_A> <INDEX_B> [-c min|max|sum|left|right]\n"
     "                       [--min-count-a <N>] [--min-count-b <N>] [-m <MIN_COUNT>] [-f <FORMAT>] [--save <SAVE>] [--sorted] [-q]\n"
     "       kmerust graph <INDEX> [-m <MIN_COUNT>] [-f summary|tsv|json] [--sorted]\n"
+    "       kmerust unitigs <INDEX> [-m <MIN_COUNT>] [-f fasta|summary]\n"
     "\n"
     "Arguments:\n"
     "  <K>     K-mer length (1-32)\n"
@@ -70,6 +71,10 @@ static const char *USAGE =
     "                        deg_<l>_<r> (nodes of left degree l and right degree r); -f json: the same as one object\n"
     "  -f tsv                {kmer}\\t{count}\\t{left}\\t{right} per node: the letters that extend it, '.' for none (--sorted:\n"
     "                        in ascending k-mer order)\n"
+    "\n"
+    "unitigs: the maximal non-branching paths of that graph, built on the device, in ascending order of their first k-mers.\n"
+    "  -f fasta (default)    >{i} LN:i:{bases} KC:i:{count sum} km:f:{mean count}, ' CR:i:1' on a circular one, then the sequence\n"
+    "  -f summary            one {name}\\t{value} line each: unitigs, kmers, bases, circular, longest, n50\n"
     "\n"
     "  -h, --help                         Print help\n"
     "  -V, --version                      Print version\n";
@@ -436,6 +441,51 @@ static int run_graph(int argc, char **argv) {
     return 0;
 }
 
+// kmerust unitigs <INDEX> [-m N] [-f fasta|summary]: the unitigs of an index's de Bruijn graph (no reference counterpart)
+static int run_unitigs(int argc, char **argv) {
+    std::string index;
+    bool have_index = false;
+    UnitigFormat fmt = UnitigFormat::Fasta;
+    uint64_t min_count = 1;
+    auto value_of = [&](int &i, const std::string &arg, const char *name) -> std::string {
+        const size_t eq = arg.find('=');
+        if (arg.rfind("--", 0) == 0 && eq != std::string::npos) return arg.substr(eq + 1);
+        if (arg.rfind("--", 0) != 0 && arg.size() > 2) return arg.substr(2);  // -fVALUE
+        if (i + 1 >= argc) usage_error(std::string("a value is required for '") + name + "' but none was supplied");
+        return argv[++i];
+    };
+    for (int i = 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        const std::string key = a.rfind("--", 0) == 0 ? a.substr(0, a.find('=')) : a.substr(0, 2);
+        if (key == "-f" || key == "--format") {
+            const std::string v = value_of(i, a, "--format <FORMAT>");
+            if (v == "fasta") fmt = UnitigFormat::Fasta;
+            else if (v == "summary") fmt = UnitigFormat::Summary;
+            else usage_error("invalid value '" + v + "' for '--format <FORMAT>'\n  [possible values: fasta, summary]");
+        } else if (key == "-m" || key == "--min-count") {
+            min_count = parse_u64(value_of(i, a, "--min-count <MIN_COUNT>"), "--min-count <MIN_COUNT>", UINT64_MAX);
+        } else if (a.size() > 1 && a[0] == '-' && a != "-") {
+            usage_error("unexpected argument '" + a + "' found");
+        } else if (!have_index) {
+            index = a;
+            have_index = true;
+        } else {
+            usage_error("unexpected argument '" + a + "' found");
+        }
+    }
+    if (!have_index) usage_error("the following required arguments were not provided:\n  <INDEX>\n\nUsage: kmerust unitigs <INDEX>");
+#if !defined(__SANITIZE_ADDRESS__) && !defined(KMERUST_UNDER_ASAN) && !defined(KMERUST_ALWAYS_CLEAN_EXIT)  // (as cli_main)
+    leak_at_exit() = !getenv("KMERUST_CLEAN_EXIT");
+#endif
+    try {
+        unitigs_index(index, min_count, fmt, stdout);
+    } catch (const Error &e) {
+        fprintf(stderr, "Application error:\n unitigs: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 static int run_query(int argc, char **argv) {
     for (int i = 2; i < argc; ++i)
         if (!strncmp(argv[i], "--sequences", 11) && (argv[i][11] == 0 || argv[i][11] == '=')) return run_query_sequences(argc, argv);
@@ -505,6 +555,7 @@ int cli_main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "compare")) return run_two_indexes(argc, argv, false);
     if (argc > 1 && !strcmp(argv[1], "combine")) return run_two_indexes(argc, argv, true);
     if (argc > 1 && !strcmp(argv[1], "graph")) return run_graph(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "unitigs")) return run_unitigs(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "__parse")) return run_parse_dump(argc, argv);
 
     std::string k_arg, path = "-", save;

@@ -36,6 +36,11 @@
 #pragma weak kh_graph_stats
 #pragma weak kh_graph_masks_device
 #pragma weak kh_graph_masks
+// ... and of `unitigs`
+#pragma weak kh_unitigs_begin
+#pragma weak kh_unitigs_copy_device
+#pragma weak kh_unitigs_copy
+#pragma weak kh_unitigs_end
 
 namespace kmerust {
 
@@ -1354,6 +1359,49 @@ void graph_index(const std::string &index, uint64_t min_count, GraphFormat fmt, 
         for (uint64_t i = 0; i < got; ++i) {
             format_graph_line(text, pc.keys[i], k, pc.counts[i], masks[i]);
             if (text.size() >= (1u << 20) || i + 1 == got) {
+                if (fwrite(text.data(), 1, text.size(), out) != text.size()) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+                text.clear();
+            }
+        }
+    }
+    if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+}
+
+// =============================================================================================
+// the unitigs of an index
+// =============================================================================================
+void write_unitig_summary(FILE *out, const UnitigSummary &u) {
+    const std::pair<const char *, uint64_t> rows[] = {{"unitigs", u.unitigs}, {"kmers", u.kmers},     {"bases", u.bases},
+                                                      {"circular", u.circular}, {"longest", u.longest}, {"n50", u.n50}};
+    for (const auto &r : rows) fprintf(out, "%s\t%llu\n", r.first, (unsigned long long)r.second);
+}
+
+void unitigs_index(const std::string &index, uint64_t min_count, UnitigFormat fmt, FILE *out) {
+    if (!kh_unitigs_begin || !kh_unitigs_copy || !kh_unitigs_copy_device || !kh_unitigs_end || !kh_merge_pairs)
+        throw Error("unitigs needs a kmerhip library with kh_unitigs_begin, kh_unitigs_copy, kh_unitigs_end and kh_merge_pairs; the one this program was built against has neither");
+    PackedCounts idx = load_index(index);
+    const uint32_t k = idx.k;
+    IndexTable t(idx, -1);
+    idx = PackedCounts();  // (the host copy is no longer needed)
+    uint64_t nu = 0, nb = 0;
+    Session::check_on(t.c, kh_unitigs_begin(t.c, min_count, &nu, &nb), "kh_unitigs_begin");
+    std::vector<uint64_t> rows(nu * KH_UNI_WORDS);
+    std::vector<uint8_t> bases(fmt == UnitigFormat::Fasta ? nb : 0);
+    Session::check_on(t.c, kh_unitigs_copy(t.c, nu ? rows.data() : nullptr, nu ? nu : 0, bases.empty() ? nullptr : bases.data(), bases.size()), "kh_unitigs_copy");
+    Session::check_on(t.c, kh_unitigs_end(t.c), "kh_unitigs_end");
+    if (fmt == UnitigFormat::Summary) {
+        write_unitig_summary(out, unitig_summary(rows.data(), nu, k));
+    } else {
+        std::string text;
+        for (uint64_t i = 0; i < nu; ++i) {
+            const uint64_t *r = rows.data() + KH_UNI_WORDS * i;
+            const uint64_t start = r[KH_UNI_START], len = r[KH_UNI_KMERS] + k - 1;
+            if (start > nb || len > nb - start) throw Error("kh_unitigs_copy returned a row outside the bases");
+            text += unitig_header(i, r, k);
+            text.push_back('\n');
+            text.append((const char *)bases.data() + start, len);
+            text.push_back('\n');
+            if (text.size() >= (1u << 20) || i + 1 == nu) {
                 if (fwrite(text.data(), 1, text.size(), out) != text.size()) throw Error(std::string("failed to write output: ") + std::strerror(errno));
                 text.clear();
             }

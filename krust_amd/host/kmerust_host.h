@@ -311,6 +311,55 @@ void write_graph_summary(FILE *out, const uint64_t *words, bool json);
 // Throws Error -- also against a library without the three kh_graph_* entry points.
 void graph_index(const std::string &index, uint64_t min_count, GraphFormat fmt, bool sorted, FILE *out);
 
+// ---- the unitigs of an index (`kmerust unitigs`; no reference counterpart) ---------------------------------------------------------------
+// The header line of unitig i, WITHOUT the newline, from its KH_UNI_WORDS row:
+//   ">{i} LN:i:{bases} KC:i:{count_sum} km:f:{count_sum / L, %.1f}" and " CR:i:1" behind it for a circular one
+// (the tags BCALM writes; bases = L + k - 1).  Pure: no device, no library call.
+inline std::string unitig_header(uint64_t i, const uint64_t *row, uint32_t k) {
+    const uint64_t L = row[KH_UNI_KMERS], cs = row[KH_UNI_COUNT_SUM];
+    char km[64];
+    snprintf(km, sizeof km, "%.1f", L ? (double)cs / (double)L : 0.0);
+    std::string h = ">" + std::to_string(i) + " LN:i:" + std::to_string(L + k - 1) + " KC:i:" + std::to_string(cs) + " km:f:" + km;
+    if (row[KH_UNI_FLAGS] & KH_UNI_CIRCULAR) h += " CR:i:1";
+    return h;
+}
+// What `kmerust unitigs -f summary` derives from the n rows: unitigs = n, kmers = the sum of L, bases = the sum of L + k - 1 (both
+// modulo 2^64), circular, longest (bases), and n50 (bases): the largest length X such that the unitigs of at least X bases hold at
+// least half of all bases -- 0 for no unitig.  Pure.
+struct UnitigSummary {
+    uint64_t unitigs = 0, kmers = 0, bases = 0, circular = 0, longest = 0, n50 = 0;
+};
+inline UnitigSummary unitig_summary(const uint64_t *rows, uint64_t n, uint32_t k) {
+    UnitigSummary u;
+    u.unitigs = n;
+    std::vector<uint64_t> len(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t *r = rows + KH_UNI_WORDS * i;
+        len[i] = r[KH_UNI_KMERS] + k - 1;
+        u.kmers += r[KH_UNI_KMERS];
+        u.bases += len[i];
+        if (r[KH_UNI_FLAGS] & KH_UNI_CIRCULAR) ++u.circular;
+        if (len[i] > u.longest) u.longest = len[i];
+    }
+    std::sort(len.begin(), len.end(), [](uint64_t a, uint64_t b) { return a > b; });
+    uint64_t run = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        run += len[i];
+        if (run >= u.bases - run) {  // (run >= half of the bases, without doubling)
+            u.n50 = len[i];
+            break;
+        }
+    }
+    return u;
+}
+enum class UnitigFormat { Fasta, Summary };
+// "{name}\t{value}" lines: unitigs, kmers, bases, circular, longest, n50.
+void write_unitig_summary(FILE *out, const UnitigSummary &u);
+// The index into a device table (as `graph` loads one), kh_unitigs_begin / kh_unitigs_copy / kh_unitigs_end; Fasta: unitig_header and
+// the unitig's bases, one record each; Summary: unitig_summary of the rows.  Throws Error -- also against a library without the four
+// kh_unitigs_* entry points.
+void unitigs_index(const std::string &index, uint64_t min_count, UnitigFormat fmt, FILE *out);
+
 // ---- KMIX index (src/index.rs) -----------------------------------------------------------------
 uint32_t crc32_ieee(const uint8_t *data, size_t n, uint32_t crc = 0);  // src/index.rs:404-431
 void save_index(const PackedCounts &pc, const std::string &path);      // gzip if path ends in .gz

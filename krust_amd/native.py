@@ -50,6 +50,10 @@ def GRAPH_LEFT(c):
     return 16 << c
 
 
+# KH_UNI_*: the words of a unitig row (kh_unitigs_*)
+UNI_WORDS, UNI_START, UNI_KMERS, UNI_COUNT_SUM, UNI_FLAGS = 4, 0, 1, 2, 3
+UNI_CIRCULAR = 1
+
 _SET_OPS = {"intersect": SET_INTERSECT, "union": SET_UNION, "subtract": SET_SUBTRACT, "count-subtract": SET_COUNT_SUBTRACT}
 _CALCS = {"min": CALC_MIN, "max": CALC_MAX, "sum": CALC_SUM, "left": CALC_LEFT, "right": CALC_RIGHT}
 
@@ -118,6 +122,10 @@ SYMBOLS = {
     "kh_graph_stats": (C.c_int, [_P, _U64, _P]),
     "kh_graph_masks_device": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_graph_masks": (C.c_int, [_P, _P, _U64, _U64, _P]),
+    "kh_unitigs_begin": (C.c_int, [_P, _U64, _P, _P]),
+    "kh_unitigs_copy_device": (C.c_int, [_P, _P, _U64, _P, _U64]),
+    "kh_unitigs_copy": (C.c_int, [_P, _P, _U64, _P, _U64]),
+    "kh_unitigs_end": (C.c_int, [_P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
     "kh_set_shard": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "kh_set_region_window": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -520,6 +528,40 @@ class DeviceCounter:
         alignment.  Returns when d_masks is complete."""
         ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
         self._check(lib().kh_graph_masks_device(self._h, ptr(d_keys), int(n), int(min_count), ptr(d_masks)))
+
+    # -- unitigs: the compacted de Bruijn graph ------------------------------
+    def unitigs_begin(self, min_count=1):
+        """kh_unitigs_begin: builds the unitigs of the node set S = the keys with a count >= max(min_count, 1) into device memory
+        of the context's own; returns (n_unitigs, n_bases).  unitigs_copy* fetch them, unitigs_end releases them."""
+        nu, nb = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().kh_unitigs_begin(self._h, int(min_count), C.byref(nu), C.byref(nb)))
+        return int(nu.value), int(nb.value)
+
+    def unitigs_copy(self, n_unitigs, n_bases):
+        """kh_unitigs_copy into fresh arrays: rows (n_unitigs, UNI_WORDS) uint64 -- START, KMERS, COUNT_SUM, FLAGS -- and the
+        bases (uint8, ASCII ACGT, unitig after unitig; a unitig of L k-mers has L + k - 1 of them)."""
+        rows = np.zeros((int(n_unitigs), UNI_WORDS), dtype=np.uint64)
+        bases = np.zeros(int(n_bases), dtype=np.uint8)
+        self._check(lib().kh_unitigs_copy(self._h, rows.ctypes.data if rows.size else None, rows.shape[0],
+                                          bases.ctypes.data if bases.size else None, bases.size))
+        return rows, bases
+
+    def unitigs_copy_device(self, d_rows, row_cap, d_bases, base_cap):
+        """The same into device memory: integer addresses or torch tensors (rows 8-byte aligned, bases at any alignment) with
+        room for row_cap rows and base_cap bases.  Returns when both are complete."""
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        self._check(lib().kh_unitigs_copy_device(self._h, ptr(d_rows), int(row_cap), ptr(d_bases), int(base_cap)))
+
+    def unitigs_end(self):
+        self._check(lib().kh_unitigs_end(self._h))
+
+    def unitigs(self, min_count=1):
+        """(rows, bases) of the unitigs of S, in ascending key order of their first nodes: begin, copy, end."""
+        nu, nb = self.unitigs_begin(min_count)
+        try:
+            return self.unitigs_copy(nu, nb)
+        finally:
+            self.unitigs_end()
 
     # -- multi-GPU merge ---------------------------------------------------
     def comm_init(self, nranks, rank, unique_id):

@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""The unitigs of a count table on the device, beside the steps to set them against (one MI355X).  Records; judges nothing.
+
+    python tools/unitig_probe.py --reads 1000000 10000000 > profiles/r13_unitig_probe.json
+
+Per size: a k = 21 table from synthetic 150 bp reads of one seed (kh_synth_reads_device).  Every figure is the median of 5 runs
+after one warm call, with the spread (max - min) of the five beside it:
+  unitigs_begin        kh_unitigs_begin(1): sort, ids, links, chain ranking, emit -- also as nodes / s
+  unitigs_copy_device  kh_unitigs_copy_device into device arrays (nothing crosses the link)
+  unitigs_copy         kh_unitigs_copy into host arrays (32 bytes per unitig and one per base over the link)
+  result_sorted_device the sort alone, begin's first step
+  graph_stats          kh_graph_stats(1): eight probes per node, as begin's index pass makes
+The measurement runs in a child process with a timeout; a failure is reported as {"error": ...}."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(fn, reps=5, warm=True):
+    if warm:
+        fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    ts.sort()
+    return {"median_s": ts[len(ts) // 2], "spread_s": ts[-1] - ts[0]}
+
+
+def measure_one(n, k):
+    import numpy as np
+    import torch
+    from krust_amd import native
+    rl = 150
+    t = torch.empty(n * (rl + 1), dtype=torch.uint8, device="cuda:0")
+    native.synth_reads_device(t.data_ptr(), None, 20260130, 1 << 28, rl, 0, n, device=0)
+    torch.cuda.synchronize()
+    a = native.DeviceCounter(k, device=0)
+    a.push_device(t.data_ptr(), None, t.numel())
+    st = a.finish()
+    del t
+    out = {"k": k, "reads": n, "table": {f: st[f] for f in ("distinct", "kmers", "table_slots", "slot_bytes")}}
+    words = a.graph_stats(1)
+    nodes = int(words[native.GRAPH_NODES])
+    nu, nb = a.unitigs_begin(1)
+    out.update(nodes=nodes, unitigs=nu, bases=nb)
+    rate = lambda r: dict(r, nodes_per_s=nodes / r["median_s"])
+    out["unitigs_begin"] = rate(timed(lambda: a.unitigs_begin(1)))
+    d_rows = torch.empty(max(4 * nu, 1), dtype=torch.int64, device="cuda:0")
+    d_bases = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    out["unitigs_copy_device"] = timed(lambda: a.unitigs_copy_device(d_rows, nu, d_bases, nb))
+    got = {}
+
+    def copy():
+        got["rows"], got["bases"] = a.unitigs_copy(nu, nb)
+
+    out["unitigs_copy"] = timed(copy)
+    rows = got["rows"]
+    assert int(np.sum(rows[:, native.UNI_KMERS], dtype=np.uint64)) == nodes
+    assert int(np.sum(rows[:, native.UNI_COUNT_SUM], dtype=np.uint64)) == int(words[native.GRAPH_KMERS])
+    assert np.array_equal(d_rows.cpu().numpy().view(np.uint64)[:4 * nu].reshape(nu, 4), rows)
+    lens = rows[:, native.UNI_KMERS] + np.uint64(k - 1)
+    out["circular"] = int(np.sum(rows[:, native.UNI_FLAGS] & np.uint64(1)))
+    out["longest_bases"] = int(lens.max()) if nu else 0
+    a.unitigs_end()
+    dk = torch.empty(nodes, dtype=torch.int64, device="cuda:0")
+    dc = torch.empty(nodes, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    out["result_sorted_device"] = rate(timed(lambda: a.result_sorted_device(dk.data_ptr(), dc.data_ptr(), nodes, 1)))
+    out["graph_stats"] = rate(timed(lambda: a.graph_stats(1)))
+    a.close()
+    return out
+
+
+def measure(args):
+    print("RESULT " + json.dumps([measure_one(n, args.k) for n in args.reads]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, nargs="+", default=[1_000_000, 10_000_000])
+    ap.add_argument("--k", type=int, default=21)
+    ap.add_argument("--timeout", type=int, default=900)
+    ap.add_argument("--child", action="store_true")
+    args = ap.parse_args()
+    if args.child:
+        measure(args)
+        return
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k), "--reads"] + [str(n) for n in args.reads]
+    try:
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
+        line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
+        res = json.loads(line[-1][7:]) if p.returncode == 0 and line else {"error": f"exit {p.returncode}", "stderr": p.stderr[-2000:]}
+    except subprocess.TimeoutExpired:
+        res = {"error": f"no result within {args.timeout} s"}
+    print(json.dumps({"probe": "unitig", "result": res}, indent=1))
+
+
+if __name__ == "__main__":
+    main()
