@@ -9,7 +9,7 @@ template <bool QUAL>
 void launch_count(kh_ctx *c, const uint8_t *abase, const uint8_t *qbase, int qaligned, u64 vbeg, u64 vend,
                   u64 wlo, u64 tile0, u64 ntiles) {
     // contiguous tile ranges per workgroup so the k-1 look-back is carried in LDS
-    u64 blocks = ntiles < (u64)GRID_CAP ? ntiles : (u64)GRID_CAP;
+    u64 blocks = ntiles < (u64)grid_cap() ? ntiles : (u64)grid_cap();
     uint32_t tpb = (uint32_t)((ntiles + blocks - 1) / blocks);
     blocks = (ntiles + tpb - 1) / tpb;
     uint32_t thr = 0;

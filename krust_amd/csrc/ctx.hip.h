@@ -23,6 +23,7 @@
 #include <sys/mman.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -57,7 +58,8 @@ constexpr u64 ACC_MAX = 8ull << 30;        // device accumulation buffer of kh_p
                                            // the whole 34 GB table: 177 ms of kernels against 74 resident.  8 GiB: two batches.)
 constexpr u64 ACC_MIN = 1ull << 20;
 constexpr u64 HALO = 32;                   // >= k-1 bytes re-sent in front of every staged chunk
-constexpr int GRID_CAP = 256 * 8;          // 256 CUs x 8 resident workgroups of 256 threads
+constexpr int GRID_CAP = 256 * 8;          // 256 CUs x 8 resident workgroups of 256 threads: the most workgroups a scanning kernel is launched
+                                           // with -- through grid_cap(), below the knobs; its grid-stride loop covers the rest
 #ifndef KH_ARENA_UNITB
 #define KH_ARENA_UNITB 128  // bytes per flushed unit of the arena level 2, 4-byte payloads (64: A/B builds)
 #endif
@@ -114,12 +116,25 @@ struct Knobs {
     u64 table_room_mb = 0;           // KMERHIP_TABLE_ROOM_MB: what the sample-sized table may take, as if the device had no more
     bool stop_after_p1 = false, stop_after_p2 = false;  // ablation builds (KH_ABL*)
     u64 profile_chunk_kb = 0;        // KMERHIP_PROFILE_CHUNK_KB: window starts per chunk of kh_profile, in units of 1024 (0: sized from the call)
+    // KMERHIP_GRID_CAP: the most workgroups of a capped-grid launch (0 / unset: GRID_CAP).  Not a field: one value per process,
+    // g_grid_cap below, which read_knobs sets -- and the context of the product library stays the size it was.
 };
 inline const char *env_of(const char *name) {
     const char *e = getenv(name);
     return (e && *e) ? e : nullptr;
 }
 void read_knobs(Knobs &k);
+
+// The cap of every launch that covers its input with a grid-stride loop (grid_for() and the launches that size their own grid).
+// The product library: the constant.  The test build: KMERHIP_GRID_CAP, so that a cap of 1 or 3 sends every workgroup round its
+// loop many times at the sizes tests/ use (tests/test_gpu_grid_stride.py) -- one value per process, set by read_knobs (grid_for is
+// a free function: the contexts of a process share it).  No kernel behind it waits for another workgroup.
+#if KH_TESTING
+extern std::atomic<int> g_grid_cap;  // (contexts on several threads re-read the switches: every one writes the same value)
+inline int grid_cap() { return g_grid_cap.load(std::memory_order_relaxed); }
+#else
+constexpr int grid_cap() { return GRID_CAP; }
+#endif
 
 }  // namespace khi
 
@@ -370,7 +385,7 @@ inline int fail(kh_ctx *c, int code, const char *what, hipError_t e = hipSuccess
 inline int grid_for(u64 items) {
     u64 b = (items + kh::BLOCK - 1) / kh::BLOCK;
     if (b < 1) b = 1;
-    if (b > (u64)GRID_CAP) b = GRID_CAP;
+    if (b > (u64)grid_cap()) b = grid_cap();
     return (int)b;
 }
 

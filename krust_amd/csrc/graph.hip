@@ -157,7 +157,7 @@ int graph_enter(kh_ctx *c, const char *who) {
 // One launch of graph_kernel on c's stream: the source against c's own table in the form it is in.
 template <typename SRC, typename SINK>
 int graph_launch_on(kh_ctx *c, SRC sv, u64 s0, u64 s1, u64 groups, u64 min_count, SINK sink, uint32_t shift) {
-    const unsigned blocks = (unsigned)std::min<u64>(groups, (u64)GRID_CAP);
+    const unsigned blocks = (unsigned)std::min<u64>(groups, (u64)grid_cap());
     // (a slot source is the context's own table: only the probe of the same form is instantiated with it)
     if constexpr (!std::is_same<SRC, kh::JsWide>::value) {
         if (c->narrow)

@@ -467,7 +467,7 @@ int scan_text(kh_ctx *c, const uint8_t *d_text, u64 n, int format, hipStream_t s
         return KH_OK;
     };
     if ((rc = tbuf(&c->txt_err, &c->txt_err_cap, (u64)4, "hipMalloc(text err)")) != KH_OK) return rc;
-    const unsigned grid = (unsigned)std::min<u64>(ntiles, (u64)GRID_CAP);
+    const unsigned grid = (unsigned)std::min<u64>(ntiles, (u64)grid_cap());
     u64 out_len = 0;
     {
         StageTimer tm(c, ST_TEXT, s);
@@ -513,7 +513,7 @@ int scan_text(kh_ctx *c, const uint8_t *d_text, u64 n, int format, hipStream_t s
             if ((rc = tbuf(&c->txt_st, &c->txt_st_cap, nunits + 1, "hipMalloc(line states)")) != KH_OK) return rc;
             if ((rc = tbuf(&c->txt_tkeep, &c->txt_tkeep_cap, ntiles, "hipMalloc(text tiles)")) != KH_OK) return rc;
             if ((rc = tbuf(&c->txt_tout, &c->txt_tout_cap, ntiles + 1, "hipMalloc(text tiles)")) != KH_OK) return rc;
-            hipLaunchKernelGGL(kh::fasta_line_state_kernel, dim3((unsigned)std::min<u64>((nunits + 3) / 4, (u64)GRID_CAP)), dim3(kh::BLOCK),
+            hipLaunchKernelGGL(kh::fasta_line_state_kernel, dim3((unsigned)std::min<u64>((nunits + 3) / 4, (u64)grid_cap())), dim3(kh::BLOCK),
                                0, s, d_text, n, nunits, c->txt_st);
             hipLaunchKernelGGL(kh::fasta_compact_kernel<0>, dim3(grid), dim3(kh::BLOCK), 0, s, d_text, n, ntiles,
                                (const uint8_t *)c->txt_st, c->txt_tkeep, (const u64 *)nullptr, (uint8_t *)nullptr, c->txt_err);

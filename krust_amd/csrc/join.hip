@@ -167,7 +167,7 @@ template <typename SINK>
 int join_launch(kh_ctx *on, const kh_ctx *src, u64 s0, u64 s1, u64 min_src, const kh_ctx *prb, u64 min_prb, SINK sink) {
     if (s1 <= s0) return KH_OK;
     const u64 ntiles = (s1 - s0 + (u64)kh::JOIN_PER * kh::BLOCK - 1) / ((u64)kh::JOIN_PER * kh::BLOCK);
-    const unsigned blocks = (unsigned)std::min<u64>(ntiles, (u64)GRID_CAP);
+    const unsigned blocks = (unsigned)std::min<u64>(ntiles, (u64)grid_cap());
     auto with_probe = [&](auto sv) {
         typedef decltype(sv) SRC;
         auto go = [&](auto pv) {

@@ -7,6 +7,10 @@
 
 namespace khi {
 
+#if KH_TESTING
+std::atomic<int> g_grid_cap{GRID_CAP};
+#endif
+
 void read_knobs(Knobs &k) {
     k = Knobs();
     if (const char *e = env_of("KMERHIP_TRACE")) k.trace = e[0] != '0';
@@ -40,6 +44,9 @@ void read_knobs(Knobs &k) {
     k.stop_after_p1 = env_of("KMERHIP_STOP_AFTER_P1") != nullptr;
     k.stop_after_p2 = env_of("KMERHIP_STOP_AFTER_P2") != nullptr;
     if (const char *e = env_of("KMERHIP_PROFILE_CHUNK_KB")) k.profile_chunk_kb = strtoull(e, nullptr, 10);
+    const char *gc = env_of("KMERHIP_GRID_CAP");
+    const int cap = gc ? atoi(gc) : 0;
+    g_grid_cap.store((cap > 0 && cap < GRID_CAP) ? cap : GRID_CAP, std::memory_order_relaxed);
 #endif
 }
 

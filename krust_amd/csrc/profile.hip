@@ -403,7 +403,7 @@ int profile_range(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 
     }
     // the window that starts at entry i ends at position vbeg + i + k - 1
     const u64 ntiles = (vbeg + (c->k - 1) + nout + kh::TILE - 1) / kh::TILE;
-    u64 blocks = ntiles < (u64)GRID_CAP ? ntiles : (u64)GRID_CAP;
+    u64 blocks = ntiles < (u64)grid_cap() ? ntiles : (u64)grid_cap();
     const uint32_t tpb = (uint32_t)((ntiles + blocks - 1) / blocks);  // contiguous tiles per workgroup: the look-back is carried in LDS
     blocks = (ntiles + tpb - 1) / tpb;
     auto launch = [&](auto tab) {
