@@ -27,6 +27,7 @@
 // same multiset of (key,count) as the direct path.
 #pragma once
 #include <type_traits>
+#include "arena_bits.h"
 #include "part_common.hip.h"
 
 namespace kh {
@@ -678,6 +679,9 @@ __global__ __launch_bounds__(P2L_NT) void part2_scatter_lines_kernel(const PT *_
 // buckets: 256 bytes each at 512; rank atomic -> bin, flush of whole units after half a batch); a payload whose rank
 // does not fit its bin goes to the overflow list too.
 // If the list itself would overflow (ovf[1] set), the host runs the exact count -> scan -> scatter path for the batch.
+// The kernel's instruction stream is kept as lean as level 1's (profiles/README.md r14_l2lean: 14 vector instructions per payload):
+// whole-chunk 16-byte loads with scalar chunk ids, byte-counting bucket counters (arena_bits.h: the bin address is one
+// shift-add / 24-bit multiply-add), one test of the OR-ed ranks per half batch, a straight-line flush.
 
 // bstart[r] for r = (p, b): arenas of cap_p = align32(ceil(n_p / P2) * 5 / 4 + 1024) payloads, partition after partition
 // ovf[1] = 2 if some partition holds more than skew_x times the mean (one workgroup handles a whole partition: a
@@ -775,16 +779,17 @@ __global__ __launch_bounds__(P2L_NT) void part2_arena_kernel(ChunkSrc cs, const 
         else return (PT)w;
     };
     constexpr int HALF = PER / 2;
-    constexpr uint32_t CAP = 256 / sizeof(PT);                // payloads per bin at 512 buckets (256 bytes)
-    // payloads all bins hold together: 128 KiB -- 144 KiB in the 768-bucket instance (round 5), which is what the CU's 160 KiB
-    // leave beside the counters, the chunk list and the positions: at 640 buckets a bin then holds 56 payloads instead of 48, and
+    constexpr uint32_t PB = (uint32_t)sizeof(PT);
+    // bytes all bins hold together (arena_bits.h): 128 KiB, 256 bytes a bin at 512 buckets -- 144 KiB in the 768-bucket instance
+    // (round 5), which is what the CU's 160 KiB leave beside the counters, the chunk list and the positions: at 640 buckets a
+    // bin then holds 56 payloads instead of 48, and
     // that is the room a whole-LINE unit (32 payloads) needs beside a half batch's arrivals (12.8 +- 3.6: with 48 the bins
     // overflowed into the list 1.5 % of the time and ate what the 128-byte units had won -- profiles/README.md r04a, 2)
-    constexpr uint32_t TOTAL = NBK == 768 ? (144u << 10) / (uint32_t)sizeof(PT) : P2L_NBK * CAP;
-    constexpr uint32_t UW = UNITB / 16;                       // 16-byte words per unit
+    constexpr uint32_t TOTALB = arena_total_bytes(NBK), TOTAL = TOTALB / PB, TRASHB = arena_trash_addr(NBK);
+    constexpr uint32_t UW = UNITB / ARENA_WORD;               // 16-byte words per unit
     static_assert(NBK == 512 || NBK == 768 || (NBK == 1024 && UNITB == 64), "1024 buckets: 128-byte bins, 64-byte units");
     __shared__ __attribute__((aligned(16))) PT s_bin[TOTAL + UNIT];  // 128 KiB (+ a trash unit)
-    __shared__ uint32_t s_cnt[NBK];
+    __shared__ uint32_t s_cnt[NBK];  // BYTES in the bin (a rank atomic returns the payload's byte offset, as in part1_bins_kernel)
     __shared__ uint32_t s_chk[CPB];
     __shared__ uint16_t s_cfill[CPB];
     __shared__ u64 s_ovf_next, s_ovf_end;  // the workgroup's private segment of the overflow list (none to begin with)
@@ -800,8 +805,18 @@ __global__ __launch_bounds__(P2L_NT) void part2_arena_kernel(ChunkSrc cs, const 
     __syncthreads();
     if (s_skip) return;
     const uint32_t P2 = g.b2;
-    // payloads per bin: the 128 KiB are shared out among the partition's P2 buckets (whole 16-byte words)
-    const uint32_t capr = POW2 ? TOTAL >> g.p2_bits : (TOTAL / P2) & ~(16u / (uint32_t)sizeof(PT) - 1u);
+    // bytes per bin: the 128 KiB are shared out among the partition's P2 buckets (whole 16-byte words)
+    const uint32_t binB = POW2 ? arena_bin_bytes_pow2(NBK, g.p2_bits) : arena_bin_bytes(NBK, P2);
+    const uint32_t bsh = arena_bin_shift(NBK, g.p2_bits);  // (POW2)
+    auto bin_addr = [&](uint32_t b, uint32_t rank) -> uint32_t {
+        if constexpr (POW2) return arena_addr_pow2(b, bsh, rank);
+        else return arena_addr_mul(b, binB, rank);
+    };
+    typedef __attribute__((address_space(3))) char lds_char;
+    typedef __attribute__((address_space(3))) PT lds_pay;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // (a plain vector: the host pass cannot copy a uint4 out of another address space)
+    typedef __attribute__((address_space(3))) u32x4 lds_u128;
+    lds_char *const bins = (lds_char *)s_bin;
     if (tid == 0) {
         s_ovf_next = 0;
         s_ovf_end = 0;
@@ -826,11 +841,13 @@ __global__ __launch_bounds__(P2L_NT) void part2_arena_kernel(ChunkSrc cs, const 
     // Round 4 (any number of buckets up to 1024, kernels.hip.h TableGeom): NBK = 768 for 513 .. 768 buckets -- three buckets per
     // lane group instead of four, 40-48 payloads per bin instead of 32.
     constexpr bool POS_LDS = NBK > 512 || KH_ARENA_POS_LDS != 0;  // (in registers they spill there: 222 / 518 VGPRs at 768 / 1024 buckets, -Rpass-analysis)
-    constexpr bool BASE_CALC = POS_LDS;
+    constexpr bool BASE_CALC = POS_LDS || !POW2;  // (the multiply-add form of the 512-bucket instance has no four registers to spare for its two addresses)
     __shared__ uint32_t s_apos[POS_LDS ? NBK : 1];
-    const uint32_t acap = pcap[p];
+    // Positions are kept in BYTES like the counters (an arena is far below 4 GiB), and what the registers hold per bucket is the
+    // lane's own store address: the arena's start plus the 16-byte word this lane writes of every unit.
+    const uint32_t acap = pcap[p], acapB = acap * PB;
     const u64 pbase = bstart[(u64)p * P2];
-    u64 abase_r[BASE_CALC ? 1 : NB];
+    char *dst_r[BASE_CALC ? 1 : NB];
     uint32_t apos_r[POS_LDS ? 1 : NB];
     if constexpr (POS_LDS) {
         if (tid < NBK) s_apos[tid] = 0;
@@ -838,16 +855,21 @@ __global__ __launch_bounds__(P2L_NT) void part2_arena_kernel(ChunkSrc cs, const 
 #pragma unroll
         for (uint32_t it = 0; it < NB; ++it) {
             const uint32_t ob = og + it * (NT / LP);
-            if constexpr (!BASE_CALC) abase_r[it] = ob < P2 ? bstart[(u64)p * P2 + ob] : 0;
+            if constexpr (!BASE_CALC) dst_r[it] = reinterpret_cast<char *>(out + (ob < P2 ? bstart[(u64)p * P2 + ob] : 0)) + oi * ARENA_WORD;
             apos_r[it] = 0;
         }
     }
-    auto abase_of = [&](uint32_t it, uint32_t ob) -> u64 {
+    auto dst_of = [&](uint32_t it, uint32_t ob) -> char * {
+        if constexpr (BASE_CALC) return reinterpret_cast<char *>(out + pbase + (u64)ob * acap) + oi * ARENA_WORD;
+        else return dst_r[it];
+    };
+    // (the rare paths -- a full arena, the final drain -- want the arena's start as a payload index)
+    auto abase_of = [&](uint32_t ob) -> u64 {
         if constexpr (BASE_CALC) return pbase + (u64)ob * acap;
-        else return abase_r[it];
+        else return bstart[(u64)p * P2 + ob];
     };
     if (tid < NBK) s_cnt[tid] = 0;
-    const uint32_t woff = (uint32_t)tid & (CHUNK_PAY - 1);  // offset inside the chunk
+    const uint32_t lane = (uint32_t)tid & 63u;
     // Appends k entries of this lane to the overflow list; false if the list is full (the host then redoes the batch).
     // On skewed input MANY lanes of MANY workgroups do this: the list is handed out in private segments (one global
     // atomic per OVF_SEG entries and workgroup, LDS atomics inside), a request that finds the segment short takes its
@@ -889,94 +911,161 @@ __global__ __launch_bounds__(P2L_NT) void part2_arena_kernel(ChunkSrc cs, const 
         __syncthreads();
         const uint32_t nchk = (uint32_t)(pb.hi - pb.lo);
         const uint32_t n = nchk * CHUNK_PAY;
-        auto load_batch = [&](uint32_t first, IT (&pay)[PER], uint32_t &have) {  // (as in part2_scatter_lines_kernel)
-            have = 0;
-            const uint32_t myci = (first >> 8) + ((uint32_t)tid & (PER - 1)) * (NT / CHUNK_PAY) + ((uint32_t)tid >> 8);
+        // A WAVE TAKES WHOLE CHUNKS, 16 bytes per lane and load: a chunk of 4-byte payloads is one load instruction of the wave, one
+        // of 8-byte payloads two, and a lane holds four payloads of each of its wave's NCH chunks.  Chunk id and fill are
+        // wave-uniform (scalar registers), the address is the chunk's base plus the lane's offset, and nothing is clamped: a chunk
+        // belongs to the pool whole, so what lies behind its fill is read and dropped (`have`).  Where every chunk of the wave is
+        // full -- nineteen batches in twenty -- `have` is a constant; the per-payload compares are behind that uniform test.
+        constexpr int NCH = PER / 4, LPC = (int)sizeof(IT) / 4;  // chunks per wave and batch, loads per chunk
+        auto load_batch = [&](uint32_t first, IT (&pay)[PER], uint32_t &have) {
+            const uint32_t myci = (first >> 8) + ((uint32_t)tid >> 6) * NCH + (lane & (NCH - 1));
             const uint32_t mycc = myci < nchk ? myci : nchk - 1;
             const uint32_t mychunk = s_chk[mycc];
             const uint32_t myfill = myci < nchk ? (uint32_t)s_cfill[mycc] : 0u;
+            uint32_t fillc[NCH];
+            bool full = true;
 #pragma unroll
-            for (int j = 0; j < PER; ++j) {
-                const uint32_t chunk = __builtin_amdgcn_readlane(mychunk, j);
-                const uint32_t fillc = __builtin_amdgcn_readlane(myfill, j);
-                const bool ok = woff < fillc;
-                pay[j] = reinterpret_cast<const IT *>(cs.pay)[(u64)chunk * CHUNK_PAY + (ok ? woff : 0u)];
-                have |= (uint32_t)ok << j;
+            for (int c = 0; c < NCH; ++c) {
+                const uint32_t chunk = __builtin_amdgcn_readlane(mychunk, c);
+                fillc[c] = __builtin_amdgcn_readlane(myfill, c);
+                full = full && fillc[c] == CHUNK_PAY;
+                const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(cs.pay) + (u64)chunk * (CHUNK_PAY * sizeof(IT)));
+#pragma unroll
+                for (int q = 0; q < LPC; ++q) {
+                    const uint4 v = src[q * 64 + lane];
+                    if constexpr (sizeof(IT) == 4) {
+                        pay[4 * c] = (IT)v.x, pay[4 * c + 1] = (IT)v.y, pay[4 * c + 2] = (IT)v.z, pay[4 * c + 3] = (IT)v.w;
+                    } else {
+                        pay[4 * c + 2 * q] = (IT)(((u64)v.y << 32) | v.x);
+                        pay[4 * c + 2 * q + 1] = (IT)(((u64)v.w << 32) | v.z);
+                    }
+                }
+            }
+            have = (1u << PER) - 1u;
+            if (!full) {  // (uniform) a load brought the lane G consecutive payloads of the chunk, from its 4 lane th (8-byte: 128 q + 2 lane th) on
+                constexpr int G = 4 / LPC;
+                have = 0;
+#pragma unroll
+                for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                    for (int q = 0; q < LPC; ++q) {
+                        const int left = (int)fillc[c] - (int)((uint32_t)q * 128u + (uint32_t)G * lane);
+                        have |= ((1u << (uint32_t)min(max(left, 0), G)) - 1u) << (4 * c + G * q);
+                    }
             }
         };
-        // the lane group writes the whole units of its buckets' bins to their arenas (or, an arena full, its first lane to the overflow list)
-        // (A/B, round 5, hg-shaped input through the 1024-bucket instance: interleaving two buckets' flushes, or skipping the
-        //  bins that hold less than a unit, changed nothing -- 10.2-10.3 ms either way; the instance is bound by the chain of its
-        //  phases between barriers with ONE workgroup per CU, like the 512-bucket one, at half the payloads per flush)
-        auto flush = [&]() {
-#pragma unroll POS_LDS ? 1 : NB
-            for (uint32_t it = 0; it < NB; ++it) {
-                const uint32_t ob = og + it * (NT / LP);
-                if (ob >= P2) continue;
-                const u64 abase = abase_of(it, ob);
-                uint32_t apos;
-                if constexpr (POS_LDS) apos = s_apos[ob];
-                else apos = apos_r[it];
-                uint4 *const bin4 = reinterpret_cast<uint4 *>(s_bin + ob * capr);
-                const uint32_t c = min(s_cnt[ob], capr);  // (ranks beyond the bin went to the overflow list)
-                const uint32_t nun = c / UNIT, r = c % UNIT;
-                for (uint32_t u = 0; u < nun; ++u) {
-                    if (apos + UNIT <= acap) {
-                        uint4 *d = reinterpret_cast<uint4 *>(out + abase + apos);
-                        // (named values, not a local array: the compiler kept `uint4 x[2]` on the stack and stored its
-                        //  second word to scratch with every unit -- 16 dead bytes per lane and unit, found in the ISA)
-                        if constexpr (UW / LP == 2) {
-                            const uint4 x0 = bin4[UW * u + oi], x1 = bin4[UW * u + oi + LP];
-                            d[oi] = x0;
-                            d[oi + LP] = x1;
-                        } else if constexpr (UW / LP == 1) {
-                            d[oi] = bin4[UW * u + oi];
-                        } else {
-                            uint4 x[UW / LP];
+        // (the arena-full form of the flush, out of line: a heavy hitter's bucket -- every later unit of it comes this way)
+        auto flush_full_arena = [&](uint32_t ob, uint32_t bw, uint32_t nun, uint32_t aposB, char *dst) -> uint32_t {
+            for (uint32_t u = 0; u < nun; ++u) {
+                if (aposB + UNITB <= acapB) {
 #pragma unroll
-                            for (uint32_t q = 0; q < UW / LP; ++q) x[q] = bin4[UW * u + oi + LP * q];
-#pragma unroll
-                            for (uint32_t q = 0; q < UW / LP; ++q) d[oi + LP * q] = x[q];
-                        }
-                        apos += UNIT;
-                    } else {
-                        // The arena is full (a heavy hitter's bucket: every later unit of it comes this way): the group's first
-                        // lane takes the room, ALL its lanes write entries -- consecutive lanes consecutive entries.  (One lane
-                        // writing the unit's 16 or 32 entries one after the other was a chain of as many stores on the way to
-                        // the barrier, in some wave at nearly every flush of an hg-shaped batch: 4 % of its payloads come here.)
-                        u64 at = 0;
-                        bool room = false;
-                        if (oi == 0) room = ovf_take(UNIT, at);
-                        const int src = (int)((uint32_t)tid & 63u & ~(LP - 1u));
-                        at = (u64)__shfl((unsigned long long)at, src, 64);
-                        room = __shfl((int)room, src, 64) != 0;
-                        if (room) {
-                            const PT *e = s_bin + ob * capr + u * UNIT;
-                            for (uint32_t q = oi; q < (uint32_t)UNIT; q += LP) {
-                                OvfEntry oe;
-                                oe.region = p * P2 + ob;
-                                oe.pad = 0;
-                                oe.pay = (u64)e[q];
-                                ovf_list[at + q] = oe;
-                            }
+                    for (uint32_t q = 0; q < UW / LP; ++q)
+                        *reinterpret_cast<u32x4 *>(dst + aposB + q * LP * ARENA_WORD) = *(lds_u128 *)(bins + bw + arena_unit_word(0, UNITB, u, q * LP));
+                    aposB += UNITB;
+                } else {
+                    // The group's first lane takes the room, ALL its lanes write entries -- consecutive lanes consecutive entries.
+                    // (One lane writing the unit's 16 or 32 entries one after the other was a chain of as many stores on the way to
+                    // the barrier, in some wave at nearly every flush of an hg-shaped batch: 4 % of its payloads come here.)
+                    u64 at = 0;
+                    bool room = false;
+                    if (oi == 0) room = ovf_take(UNIT, at);
+                    const int src = (int)(lane & ~(LP - 1u));
+                    at = (u64)__shfl((unsigned long long)at, src, 64);
+                    room = __shfl((int)room, src, 64) != 0;
+                    if (room) {
+                        const uint32_t e = bin_addr(ob, u * UNITB);
+                        for (uint32_t q = oi; q < (uint32_t)UNIT; q += LP) {
+                            OvfEntry oe;
+                            oe.region = p * P2 + ob;
+                            oe.pad = 0;
+                            oe.pay = (u64) * (lds_pay *)(bins + e + q * PB);
+                            ovf_list[at + q] = oe;
                         }
                     }
                 }
-                __builtin_amdgcn_wave_barrier();
-                if (nun) {
-                    const uint32_t nw = (r * (uint32_t)sizeof(PT) + 15u) / 16u;
-                    uint4 m[UW / LP];
+            }
+            return aposB;
+        };
+        // STRAIGHT-LINE, as part1_bins_kernel's: a bin of the instance's smallest geometry holds at most KS whole units, written as
+        // KS predicated steps (the first unconditional: a bin that holds less than a unit is left alone altogether); a loop behind
+        // them takes what the larger bins of fewer buckets can hold beyond that.  Whether the arena has room for all the units is
+        // decided ONCE per bucket and flush.
+        constexpr uint32_t KS = NBK == 1024 ? 2u : 256u / (uint32_t)UNITB;
+        auto flush = [&]() {
+#pragma unroll POS_LDS ? 1 : NB
+            for (uint32_t it = 0; it < NB; ++it) {
+                uint32_t ob = og + it * (NT / LP);
+                if (ob >= P2) continue;
+                // (multiply-add forms: the bucket's addresses are worked out here, one instruction each -- kept in registers from
+                //  the kernel's start they were the two the 512-bucket instance then spilled)
+                if constexpr (!POW2) asm volatile("" : "+v"(ob));
+                const uint32_t cB = min(s_cnt[ob], binB);  // (ranks beyond the bin went to the overflow list)
+                const uint32_t nun = cB / (uint32_t)UNITB, rB = cB % (uint32_t)UNITB;
+                if (nun == 0) continue;
+                const uint32_t bw = bin_addr(ob, oi * ARENA_WORD);  // this lane's first word of the bin's first unit
+                uint32_t aposB;
+                if constexpr (POS_LDS) aposB = s_apos[ob];
+                else aposB = apos_r[it];
+                char *const dst = dst_of(it, ob);
+                lds_char *const bp = bins + bw;
+                if (__builtin_expect(aposB + nun * (uint32_t)UNITB <= acapB, 1)) {
+                    char *const d = dst + aposB;
+                    // (named values, not a local array: the compiler kept `uint4 x[2]` on the stack and stored its second word to
+                    //  scratch with every unit -- found in the ISA; the words' LDS addresses are the lane's plus a constant)
+                    auto unit = [&](uint32_t u) {
+                        lds_char *const b = bp + arena_unit_word(0, UNITB, u, 0);
+                        char *const du = d + u * (uint32_t)UNITB;
+                        if constexpr (UW / LP == 2) {
+                            const u32x4 x0 = *(lds_u128 *)b, x1 = *(lds_u128 *)(b + LP * ARENA_WORD);
+                            *reinterpret_cast<u32x4 *>(du) = x0;
+                            *reinterpret_cast<u32x4 *>(du + LP * ARENA_WORD) = x1;
+                        } else if constexpr (UW / LP == 1) {
+                            *reinterpret_cast<u32x4 *>(du) = *(lds_u128 *)b;
+                        } else {
+                            u32x4 x[UW / LP];
 #pragma unroll
-                    for (uint32_t q = 0; q < UW / LP; ++q) m[q] = oi + LP * q < nw ? bin4[UW * nun + oi + LP * q] : make_uint4(0, 0, 0, 0);
+                            for (uint32_t q = 0; q < UW / LP; ++q) x[q] = *(lds_u128 *)(b + q * LP * ARENA_WORD);
 #pragma unroll
-                    for (uint32_t q = 0; q < UW / LP; ++q)
-                        if (oi + LP * q < nw) bin4[oi + LP * q] = m[q];
-                }
-                if (oi == 0) s_cnt[ob] = r;
-                if constexpr (POS_LDS) {
-                    if (oi == 0) s_apos[ob] = apos;  // (the group's lanes read it together at the top: same wave, next flush is behind barriers)
+                            for (uint32_t q = 0; q < UW / LP; ++q) *reinterpret_cast<u32x4 *>(du + q * LP * ARENA_WORD) = x[q];
+                        }
+                    };
+                    unit(0);
+#pragma unroll
+                    for (uint32_t u = 1; u < KS; ++u)
+                        if (u < nun) unit(u);
+                    if (nun > KS) {  // (fewer buckets, larger bins; the start hidden from the compiler, or it keeps this loop's addresses in registers all along)
+                        uint32_t u = KS;
+                        asm volatile("" : "+v"(u));
+                        for (; u < nun; ++u) unit(u);
+                    }
+                    aposB += nun * (uint32_t)UNITB;
                 } else {
-                    apos_r[it] = apos;
+                    aposB = flush_full_arena(ob, bw, nun, aposB, dst);
+                }
+                __builtin_amdgcn_wave_barrier();
+                {  // what is left behind the whole units moves to the front of the bin
+                    const uint32_t nw = (rB + ARENA_WORD - 1u) / ARENA_WORD;
+                    lds_char *const from = bp + nun * (uint32_t)UNITB;
+                    if constexpr (UW / LP <= 2) {
+                        u32x4 m0 = (u32x4)(0u), m1 = m0;
+                        if (oi < nw) m0 = *(lds_u128 *)from;
+                        if (UW / LP == 2 && oi + LP < nw) m1 = *(lds_u128 *)(from + LP * ARENA_WORD);
+                        if (oi < nw) *(lds_u128 *)bp = m0;
+                        if (UW / LP == 2 && oi + LP < nw) *(lds_u128 *)(bp + LP * ARENA_WORD) = m1;
+                    } else {
+                        u32x4 m[UW / LP];
+#pragma unroll
+                        for (uint32_t q = 0; q < UW / LP; ++q) m[q] = oi + LP * q < nw ? *(lds_u128 *)(from + q * LP * ARENA_WORD) : (u32x4)(0u);
+#pragma unroll
+                        for (uint32_t q = 0; q < UW / LP; ++q)
+                            if (oi + LP * q < nw) *(lds_u128 *)(bp + q * LP * ARENA_WORD) = m[q];
+                    }
+                }
+                if (oi == 0) s_cnt[ob] = rB;
+                if constexpr (POS_LDS) {
+                    if (oi == 0) s_apos[ob] = aposB;  // (the group's lanes read it together at the top: same wave, next flush is behind barriers)
+                } else {
+                    apos_r[it] = aposB;
                 }
             }
         };
@@ -998,17 +1087,30 @@ __global__ __launch_bounds__(P2L_NT) void part2_arena_kernel(ChunkSrc cs, const 
                 for (int j = 0; j < HALF; ++j) {
                     pay[h * HALF + j] = l2_finish(pay[h * HALF + j], p, g);  // (level 1 left the last Feistel round to us)
                     dg[j] = digit(pay[h * HALF + j]);
-                    if constexpr (FULL) rk[j] = atomicAdd(&s_cnt[dg[j]], 1u);
-                    else rk[j] = ((have >> (h * HALF + j)) & 1u) ? atomicAdd(&s_cnt[dg[j]], 1u) : 0xFFFFFFFFu;
+                    if constexpr (FULL) rk[j] = atomicAdd(&s_cnt[dg[j]], PB);
+                    else rk[j] = ((have >> (h * HALF + j)) & 1u) ? atomicAdd(&s_cnt[dg[j]], PB) : 0xFFFFFFFFu;
                 }
-                uint32_t omask = 0;
+                // The store: bin address and byte rank in one shift-add (multiply-add), a rank beyond the bin -- or "no payload" --
+                // to the trash word.  FULL: the ranks are put together (OR where a bin is a power of two bytes, else max) and
+                // tested ONCE; which of them did not fit is worked out only behind that test.
+                uint32_t omask = 0, racc = 0;
 #pragma unroll
                 for (int j = 0; j < HALF; ++j) {
                     const uint32_t r = rk[j];
-                    s_bin[r < capr ? dg[j] * capr + r : TOTAL] = kept(pay[h * HALF + j]);
-                    omask |= (r != 0xFFFFFFFFu && r >= capr) ? (1u << j) : 0u;
+                    *(lds_pay *)(bins + (r < binB ? bin_addr(dg[j], r) : TRASHB)) = kept(pay[h * HALF + j]);
+                    if constexpr (!FULL) omask |= (r != 0xFFFFFFFFu && r >= binB) ? (1u << j) : 0u;
+                    else if constexpr (POW2) racc |= r;
+                    else racc = max(racc, r);
                 }
-                if (kh_any(omask != 0)) {  // ranks that did not fit their bins (a heavy bucket): straight to the overflow list
+                bool over;
+                if constexpr (FULL) over = kh_any(racc >= binB);
+                else over = kh_any(omask != 0);
+                if (over) {  // ranks that did not fit their bins (a heavy bucket): straight to the overflow list
+                    if constexpr (FULL) {
+#pragma unroll
+                        for (int j = 0; j < HALF; ++j) omask |= rk[j] >= binB ? (1u << j) : 0u;
+                        asm volatile("" : "+v"(omask));  // (or the compiler works the eight conditions out again in front of the test)
+                    }
                     const uint32_t k = (uint32_t)__builtin_popcount(omask);
                     // ONE request per wave (round 5): the lanes' counts are scanned in the wave and its last lane asks for the
                     // sum -- with repeats in the input (4 % of an hg-shaped batch's payloads come here) some twenty lanes of
@@ -1080,12 +1182,12 @@ __global__ __launch_bounds__(P2L_NT) void part2_arena_kernel(ChunkSrc cs, const 
     for (uint32_t it = 0; it < NB; ++it) {
         const uint32_t ob = og + it * (NT / LP);
         if (oi != 0 || ob >= P2) continue;
-        const uint32_t r = s_cnt[ob];
-        const PT *bin = s_bin + ob * capr;
-        const u64 abase = abase_of(it, ob);
+        const uint32_t r = s_cnt[ob] / PB;  // (bytes; below a unit after the last flush)
+        const lds_pay *bin = (const lds_pay *)(bins + bin_addr(ob, 0));
+        const u64 abase = abase_of(ob);
         uint32_t apos;
-        if constexpr (POS_LDS) apos = s_apos[ob];
-        else apos = apos_r[it];
+        if constexpr (POS_LDS) apos = s_apos[ob] / PB;
+        else apos = apos_r[it] / PB;
         if (r) {
             if (apos + r <= acap) {
                 for (uint32_t i = 0; i < r; ++i) out[abase + apos + i] = bin[i];
