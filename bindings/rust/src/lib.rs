@@ -124,6 +124,10 @@ pub mod sys {
         pub fn kh_unitigs_copy_device(ctx: *mut KhCtx, d_rows: *mut u64, row_cap: u64, d_bases: *mut u8, base_cap: u64) -> c_int;
         pub fn kh_unitigs_copy(ctx: *mut KhCtx, rows: *mut u64, row_cap: u64, bases: *mut u8, base_cap: u64) -> c_int;
         pub fn kh_unitigs_end(ctx: *mut KhCtx) -> c_int;
+        /// `kh_unitigs_begin` plus the links between the unitigs' ends: one word per link, ascending
+        pub fn kh_unitigs_begin_linked(ctx: *mut KhCtx, min_count: u64, n_unitigs: *mut u64, n_bases: *mut u64, n_links: *mut u64) -> c_int;
+        pub fn kh_unitigs_links_copy_device(ctx: *mut KhCtx, d_links: *mut u64, cap: u64) -> c_int;
+        pub fn kh_unitigs_links_copy(ctx: *mut KhCtx, links: *mut u64, cap: u64) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
         pub fn kh_result_sorted(ctx: *mut KhCtx, keys: *mut u64, counts: *mut u64, cap: u64,
                                 min_count: u64, n: *mut u64) -> c_int;
@@ -211,6 +215,15 @@ pub const UNI_COUNT_SUM: usize = 2;
 pub const UNI_FLAGS: usize = 3;
 /// `KH_UNI_CIRCULAR`: bit 0 of the flags word -- the chain closes, and the closing overlap is not repeated in the bases.
 pub const UNI_CIRCULAR: u64 = 1;
+
+/// `KH_UNI_LINK_FROM(w)`: the unitig a link word of `kh_unitigs_links_copy` leaves (a row index of `kh_unitigs_copy`).
+pub const fn uni_link_from(w: u64) -> u32 { (w >> 33) as u32 }
+/// `KH_UNI_LINK_FROM_SIGN(w)`: 0 = it leaves the right end of the reported sequence (+), 1 = that of its reverse complement (-).
+pub const fn uni_link_from_sign(w: u64) -> u32 { ((w >> 32) & 1) as u32 }
+/// `KH_UNI_LINK_TO(w)`: the unitig the link enters.
+pub const fn uni_link_to(w: u64) -> u32 { ((w & 0xFFFF_FFFF) >> 1) as u32 }
+/// `KH_UNI_LINK_TO_SIGN(w)`: 0 = entered at the start of its reported sequence (+), 1 = at the start of its reverse complement (-).
+pub const fn uni_link_to_sign(w: u64) -> u32 { (w & 1) as u32 }
 
 /// KH_SET_*: the set operation of `kh_combine_into`.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -514,6 +527,25 @@ impl HipKmerMap {
         check(self.ctx, rc)?;
         check(self.ctx, end)?;
         Ok((rows, bases))
+    }
+
+    /// [`unitigs`](Self::unitigs) and the links between the unitigs' ends (`kh_unitigs_begin_linked` / `kh_unitigs_copy` /
+    /// `kh_unitigs_links_copy` / `kh_unitigs_end`): one word per link -- [`uni_link_from`], [`uni_link_from_sign`], [`uni_link_to`],
+    /// [`uni_link_to_sign`] take it apart --, in ascending word order; a link spans k - 1 bases of overlap.  Loops, hairpins and
+    /// the closing link of a circular unitig are links like any other.
+    pub fn unitigs_linked(&self, min_count: u64) -> Result<(Vec<u64>, Vec<u8>, Vec<u64>), HipError> {
+        let (mut nu, mut nb, mut nl) = (0u64, 0u64, 0u64);
+        check(self.ctx, unsafe { sys::kh_unitigs_begin_linked(self.ctx, min_count, &mut nu, &mut nb, &mut nl) })?;
+        let mut rows = vec![0u64; nu as usize * UNI_WORDS];
+        let mut bases = vec![0u8; nb as usize];
+        let mut links = vec![0u64; nl as usize];
+        let rc = unsafe { sys::kh_unitigs_copy(self.ctx, rows.as_mut_ptr(), nu, bases.as_mut_ptr(), nb) };
+        let rl = unsafe { sys::kh_unitigs_links_copy(self.ctx, links.as_mut_ptr(), nl) };
+        let end = unsafe { sys::kh_unitigs_end(self.ctx) };
+        check(self.ctx, rc)?;
+        check(self.ctx, rl)?;
+        check(self.ctx, end)?;
+        Ok((rows, bases, links))
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

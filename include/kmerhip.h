@@ -443,6 +443,41 @@ int kh_unitigs_copy_device(kh_ctx *ctx, uint64_t *d_rows, uint64_t row_cap, uint
 int kh_unitigs_copy(kh_ctx *ctx, uint64_t *rows, uint64_t row_cap, uint8_t *bases, uint64_t base_cap);
 int kh_unitigs_end(kh_ctx *ctx);
 
+/* ---- links between unitigs: the edges of the compacted graph (what BCALM and Cuttlefish write next to the sequences) --- */
+/* With the definitions above, every unitig i has two END STATES:
+ *   end +: the last oriented node of its reported reading -- the right end of the reported sequence;
+ *   end -: rev() of the first oriented node of its reported reading -- the right end of the reverse complement.
+ *   For L = 1 these are (x, +) and (x, -).
+ * A LINK exists for every end state e and every successor v of e: every letter whose bit is set in the four mask bits of e
+ *   (mask & 15 for sign +, mask >> 4 for sign -).  No link is special-cased away: homopolymer loops, hairpins and the closing
+ *   link of a circular unitig are links.
+ * v lies in some unitig j, which is ENTERED with sign + if v is the first oriented node of j's reported reading, with sign - if
+ *   v is rev() of its last; the first is tested first, so that a palindromic unitig (L = 1, its k-mer equal to its reverse
+ *   complement) is always entered as +.  Nothing else can happen: a successor of an end state is never interior to a unitig
+ *   (had v a compactable link in, its in-degree were 1, e its only predecessor and e -> v compactable, so e no end -- unless e
+ *   is the cut of a circular unitig, where v is that unitig's first node).  The device tests it all the same; a failure is
+ *   KH_ERR_STATE "internal error".
+ * LINK WORD: one uint64 per link, high 32 bits = 2 * from_unitig + from_sign, low 32 bits = 2 * to_unitig + to_sign, sign + = 0,
+ *   sign - = 1.  Unitig indices are the row indices of kh_unitigs_copy (fewer than 2^31).
+ * ORDER: ascending word value -- by from-unitig, + end before - end, then by to-unitig and to-sign.  Like the rows, the same
+ *   table content gives the same bytes for every geometry and table form.
+ * WHAT FOLLOWS: no word occurs twice; with (a, sa) -> (b, sb) the mirror (b, !sb) -> (a, !sa) is in the list (the sign of a
+ *   palindromic unitig counts as either); n_links is the sum of the end states' out-degrees; a circular unitig i carries
+ *   i+ -> i+ and i- -> i-; a link spans k - 1 bases of overlap (0 at k = 1).
+ * kh_unitigs_begin_linked is kh_unitigs_begin -- same entry, same rows and bases, same errors -- plus the link array, in device
+ * memory of the context's own with the same lifetime (kh_unitigs_end, the next begin of either kind, kh_reset, kh_destroy).  A
+ * NULL n_links is KH_ERR_BAD_ARG.  kh_unitigs_copy* work after either begin.
+ * The link copies enter as readers, like kh_unitigs_copy*: cap < n_links is KH_ERR_RANGE with nothing written, a NULL array
+ * with capacity 0 skips, stale or not begun is KH_ERR_STATE, and so is a copy after a plain kh_unitigs_begin, which built no
+ * links (the message names kh_unitigs_begin_linked). */
+#define KH_UNI_LINK_FROM(w) ((uint32_t)((uint64_t)(w) >> 33))
+#define KH_UNI_LINK_FROM_SIGN(w) ((uint32_t)(((uint64_t)(w) >> 32) & 1u))
+#define KH_UNI_LINK_TO(w) ((uint32_t)(((uint64_t)(w) & 0xFFFFFFFFu) >> 1))
+#define KH_UNI_LINK_TO_SIGN(w) ((uint32_t)((uint64_t)(w) & 1u))
+int kh_unitigs_begin_linked(kh_ctx *ctx, uint64_t min_count, uint64_t *n_unitigs, uint64_t *n_bases, uint64_t *n_links);
+int kh_unitigs_links_copy_device(kh_ctx *ctx, uint64_t *d_links, uint64_t cap);
+int kh_unitigs_links_copy(kh_ctx *ctx, uint64_t *links, uint64_t cap);
+
 /* ---- multi-GPU merge (no reference counterpart) ----------- */
 /* Owner shard of a packed canonical k-mer among nparts shards: a fast-range of the top bits of
  * the table hash, so a shard is a contiguous range of table regions (same function on host and

@@ -9,7 +9,7 @@
 //   profile.hip   kh_profile*: the table's count at every window start of new sequences
 //   join.hip      kh_compare / kh_combine_into: one table scanned, another probed, statistics or a third table out
 //   graph.hip     kh_graph_stats / kh_graph_masks*: the table against itself, eight probes per k-mer, its de Bruijn degrees out
-//   unitig.hip    kh_unitigs_*: the maximal non-branching paths of that graph (link rule, chain ranking by pointer doubling, emitter)
+//   unitig.hip    kh_unitigs_*: the maximal non-branching paths of that graph (link rule, chain ranking by pointer doubling, emitter, links between them)
 //   sort.hip      kh_result_sorted*: the result pairs in ascending key order (a device radix sort; format.hip streams it as text)
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
@@ -349,13 +349,16 @@ struct kh_ctx {
     u64 *jn_words = nullptr;
     // kh_graph_stats (graph.hip): the KH_GRAPH_WORDS words its kernel adds up
     u64 *gr_words = nullptr;
-    // kh_unitigs_* (unitig.hip): the rows and bases of the last kh_unitigs_begin, memory of the context's own until kh_unitigs_end /
+    // kh_unitigs_* (unitig.hip): the rows, bases and links of the last kh_unitigs_begin[_linked], memory of the context's own until kh_unitigs_end /
     // the next begin / kh_reset / kh_destroy.  `live` falls with every call that enters as a writer (enter(), reader = false).
     struct Unitigs {
         bool live = false;
         u64 *rows = nullptr;      // KH_UNI_WORDS words per unitig
         uint8_t *bases = nullptr;
         u64 n_unitigs = 0, n_bases = 0;
+        bool linked = false;      // built by kh_unitigs_begin_linked: the link words, one per (end state, successor)
+        u64 *links = nullptr;     // (nullptr when there are none)
+        u64 n_links = 0;
     } un;
 
     bool poisoned = false;
@@ -465,7 +468,7 @@ struct SortScratch {
 };
 int sorted_into(kh_ctx *c, u64 *out_keys, u64 *out_counts, u64 n, u64 min_count, SortScratch &sc);
 // ---- unitig.hip
-void unitigs_release(kh_ctx *c);  // kh_unitigs_end / kh_reset / kh_destroy: the rows and bases of the last kh_unitigs_begin
+void unitigs_release(kh_ctx *c);  // kh_unitigs_end / kh_reset / kh_destroy: the rows, bases and links of the last kh_unitigs_begin[_linked]
 // ---- profile.hip
 void profile_release(kh_ctx *c);  // kh_destroy: the chunk buffers and events of kh_profile, the rows of kh_profile_records
 

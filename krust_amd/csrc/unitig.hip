@@ -21,6 +21,12 @@
 //   unitig_place_kernel        per node: its id and sign into unitig order (4-byte stores); START
 //   unitig_sum_kernel          COUNT_SUM: a segmented sum over that order -- one atomic per (wave, unitig), never one per node
 //   unitig_bases_kernel        per 16 bytes of the base array: the letters, one aligned 16-byte store (bytes only in the array's tail)
+// kh_unitigs_begin_linked only, behind all of the above and while its scratch is live (the links between unitigs, include/kmerhip.h):
+//   unitig_end_degree_kernel   per end state (two per unitig: the last node of the reading, rev() of the first): its out-degree from the
+//                              node's mask, no probes
+//   device_scan                degrees -> offsets; their sum is the number of links
+//   unitig_link_out_kernel<PRB> per end state: its up to four successors, four first-slot loads in flight, slot -> node id -> unitig,
+//                              position and sign in the reading -> link words, sorted in registers, stored at the lane's offset (no atomics)
 // No kernel waits for another workgroup, and no device loop is without a bound.  Rates were not measured (profiles/README.md r13).
 #include "ctx.hip.h"
 #include "probe.hip.h"
@@ -291,6 +297,115 @@ KH_GLOBAL __launch_bounds__(BLOCK) void unitig_bases_kernel(const u64 *__restric
     }
 }
 
+// ---- links between unitigs (kh_unitigs_begin_linked) ------------------------------------------------------------------------
+// End state t = 2 u + e of unitig u: e = 0 the last oriented node of its reading, e = 1 rev() of its first.  Its node and sign
+// from the order array; false where the row or the order array is inconsistent (never).
+__device__ __forceinline__ bool unitig_end_state(u64 t, uint32_t n, uint32_t k, const u64 *__restrict__ rows, const uint32_t *__restrict__ order,
+                                                 uint32_t *id, uint32_t *sign) {
+    const u64 u = t >> 1;
+    const uint32_t e = (uint32_t)t & 1u;
+    const u64 st = rows[KH_UNI_WORDS * u + KH_UNI_START], L = rows[KH_UNI_WORDS * u + KH_UNI_KMERS];
+    const u64 q = st - u * (k - 1u) + (e ? 0 : L - 1);
+    *id = 0;
+    *sign = e;
+    if (q >= n) return false;
+    const uint32_t rec = order[q];
+    *id = rec & ~UNI_SIGN;
+    *sign = (rec >> 31) ^ e;
+    return *id < n;
+}
+
+// kernel-resource-usage (gfx950, hipcc -O3): 18 VGPRs, 33 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void unitig_end_degree_kernel(uint32_t n, uint32_t k, u64 nu, const u64 *__restrict__ rows,
+                                                                  const uint32_t *__restrict__ order, const uint8_t *__restrict__ masks,
+                                                                  uint32_t *__restrict__ deg, uint32_t *__restrict__ err) {
+    for (u64 t = (u64)blockIdx.x * BLOCK + threadIdx.x; t < 2 * nu; t += (u64)gridDim.x * BLOCK) {
+        uint32_t id, sign, d = 0;
+        if (unitig_end_state(t, n, k, rows, order, &id, &sign)) d = (uint32_t)__builtin_popcount(kh_unitig_out_bits(masks[id], sign));
+        else *err = 1u;
+        deg[t] = d;
+    }
+}
+
+__device__ __forceinline__ void link_cswap(u64 &a, u64 &b) {
+    const u64 lo = a < b ? a : b, hi = a < b ? b : a;
+    a = lo;
+    b = hi;
+}
+
+// Per end state: its up to four successors, all first-slot loads in flight before any probe is walked (as graph_mask_of), each
+// successor's slot -> node id -> unitig, position and sign in the reading -> the link word; the words sorted in registers (absent
+// ones are ~0 and go last) and stored at the lane's offset.
+// kernel-resource-usage (gfx950, hipcc -O3), PfNarrow / PfWide: 64 / 73 VGPRs (four probes in flight), 96 / 91 SGPRs, no LDS, no scratch, no spills,
+// 8 / 6 waves per SIMD.
+template <typename PRB>
+__global__ __launch_bounds__(BLOCK) void unitig_link_out_kernel(const u64 *__restrict__ keys, uint32_t n, uint32_t k, PRB prb, u64 cap, u64 nu,
+                                                                const u64 *__restrict__ rows, const uint32_t *__restrict__ order,
+                                                                const uint32_t *__restrict__ slot2id, const uint8_t *__restrict__ masks,
+                                                                const uint32_t *__restrict__ head, const uint32_t *__restrict__ posg,
+                                                                const u64 *__restrict__ uidx, const u64 *__restrict__ off, u64 n_links,
+                                                                u64 *__restrict__ links, uint32_t *__restrict__ err) {
+    for (u64 t = (u64)blockIdx.x * BLOCK + threadIdx.x; t < 2 * nu; t += (u64)gridDim.x * BLOCK) {
+        uint32_t id, sign;
+        const bool ok = unitig_end_state(t, n, k, rows, order, &id, &sign);
+        const u64 x = keys[id];
+        const uint32_t bits = ok ? kh_unitig_out_bits(masks[id], sign) : 0u;
+        u64 y[4];
+        uint32_t ys[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            uint64_t yy;
+            bool yp;
+            kh_unitig_successor(x, k, sign, kh_unitig_letter_of_bit(j, sign), &yy, &ys[j], &yp);
+            y[j] = ((bits >> j) & 1u) ? yy : x;  // (a key that is there: the probe below needs no branch)
+        }
+        typename PRB::Ref ref[4];
+        typename PRB::Word first[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ref[j] = prb.ref(y[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) first[j] = PRB::load(ref[j]);  // (all four first-slot loads in flight)
+        u64 w0 = ~0ull, w1 = ~0ull, w2 = ~0ull, w3 = ~0ull;
+        bool bad = !ok;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const u64 slot = prb.resolve_slot(ref[j], first[j]);
+            u64 w = ~0ull;
+            if ((bits >> j) & 1u) {
+                const uint32_t yid = slot < cap ? slot2id[slot] : n;
+                const uint32_t h = yid < n ? head[yid] : n;
+                const u64 ju = h < n ? uidx[h] : nu;
+                uint32_t es = KH_UNI_ENTER_NONE;
+                if (ju < nu) {
+                    const uint32_t pg = posg[yid];
+                    es = kh_unitig_enter_sign(pg & ~UNI_SIGN, (uint32_t)rows[KH_UNI_WORDS * ju + KH_UNI_KMERS], pg >> 31, ys[j]);
+                }
+                if (es == KH_UNI_ENTER_NONE) bad = true;
+                else w = kh_unitig_link_word((uint32_t)(t >> 1), (uint32_t)t & 1u, (uint32_t)ju, es);
+            }
+            if (j == 0) w0 = w;
+            else if (j == 1) w1 = w;
+            else if (j == 2) w2 = w;
+            else w3 = w;
+        }
+        if (bad) *err = 1u;
+        link_cswap(w0, w1);
+        link_cswap(w2, w3);
+        link_cswap(w0, w2);
+        link_cswap(w1, w3);
+        link_cswap(w1, w2);
+        const u64 o = off[t], d = off[t + 1] - o;  // (d = popcount(bits), by unitig_end_degree_kernel)
+        if (o + d > n_links || d > 4) {
+            *err = 1u;
+            continue;
+        }
+        if (d > 0) links[o] = w0;
+        if (d > 1) links[o + 1] = w1;
+        if (d > 2) links[o + 2] = w2;
+        if (d > 3) links[o + 3] = w3;
+    }
+}
+
 }  // namespace kh
 
 namespace khi {
@@ -298,6 +413,7 @@ namespace khi {
 void unitigs_release(kh_ctx *c) {
     if (c->un.rows) (void)hipFree(c->un.rows);  // (synchronises the device)
     if (c->un.bases) (void)hipFree(c->un.bases);
+    if (c->un.links) (void)hipFree(c->un.links);
     c->un = kh_ctx::Unitigs();
 }
 
@@ -334,7 +450,8 @@ int unitig_rank(kh_ctx *c, const uint32_t *next, u64 states, kh::UniRank *cur, k
     return KH_OK;
 }
 
-int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc) {
+// linked: kh_unitigs_begin_linked -- the link array behind the same kernels; nothing of it is launched or allocated without.
+int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked) {
     const uint32_t n32 = (uint32_t)n, k = c->k;
     const u64 states = 2 * n;
     u64 *const keys = (u64 *)sc.take(n * sizeof(u64));
@@ -417,12 +534,49 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc) {
     hipLaunchKernelGGL(kh::unitig_bases_kernel, dim3(uni_grid((nb + 15) / 16)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k,
                        (const uint32_t *)order, (const u64 *)ustart, nu, nb, c->un.bases);
     HIP_TRY(c, hipGetLastError());
+    // the links: every end state's out-degree -> offsets; their sum comes back with the consistency word
+    uint32_t *deg = nullptr;
+    u64 *loff = nullptr, nl = 0;
+    if (linked) {
+        deg = (uint32_t *)sc.take(2 * nu * sizeof(uint32_t));
+        loff = (u64 *)sc.take((2 * nu + 1) * sizeof(u64));
+        if (!deg || !loff) return soft_oom(c, "device memory for the unitigs' link offsets");
+        hipLaunchKernelGGL(kh::unitig_end_degree_kernel, dim3(uni_grid(2 * nu)), dim3(kh::BLOCK), 0, c->stream, n32, k, nu, (const u64 *)c->un.rows,
+                           (const uint32_t *)order, (const uint8_t *)masks, deg, d_flag + 1);
+        HIP_TRY(c, hipGetLastError());
+        if ((rc = device_scan(c, deg, 2 * nu, loff)) != KH_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(&nl, loff + 2 * nu, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    }
     uint32_t bad = 0;
     HIP_TRY(c, hipMemcpyAsync(&bad, d_flag + 1, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (bad) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: the chains are inconsistent (internal error)");
+    if (nl > 8 * nu) return fail(c, KH_ERR_STATE, "kh_unitigs_begin_linked: the end states' degrees do not add up (internal error)");
+    if (nl) {
+        if (hipMalloc((void **)&c->un.links, nl * sizeof(u64)) != hipSuccess) {
+            (void)hipGetLastError();
+            c->un.links = nullptr;
+            return soft_oom(c, "hipMalloc(unitig links)");
+        }
+        if (c->narrow) {
+            const kh::PfNarrow prb{(const u64 *)c->ntab, c->narrow_g};
+            hipLaunchKernelGGL((kh::unitig_link_out_kernel<kh::PfNarrow>), dim3(uni_grid(2 * nu)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k,
+                               prb, c->cap, nu, (const u64 *)c->un.rows, (const uint32_t *)order, (const uint32_t *)slot2id, (const uint8_t *)masks,
+                               (const uint32_t *)head, (const uint32_t *)posg, (const u64 *)uidx, (const u64 *)loff, nl, c->un.links, d_flag + 1);
+        } else {
+            const kh::PfWide prb{table_geom(c, c->table, c->cap)};
+            hipLaunchKernelGGL((kh::unitig_link_out_kernel<kh::PfWide>), dim3(uni_grid(2 * nu)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k,
+                               prb, c->cap, nu, (const u64 *)c->un.rows, (const uint32_t *)order, (const uint32_t *)slot2id, (const uint8_t *)masks,
+                               (const uint32_t *)head, (const uint32_t *)posg, (const u64 *)uidx, (const u64 *)loff, nl, c->un.links, d_flag + 1);
+        }
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(&bad, d_flag + 1, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (bad) return fail(c, KH_ERR_STATE, "kh_unitigs_begin_linked: a link enters a unitig at neither end (internal error)");
+    }
     c->un.n_unitigs = nu;
     c->un.n_bases = nb;
+    c->un.n_links = nl;
     return KH_OK;
 }
 
@@ -443,22 +597,27 @@ int unitigs_copy_enter(kh_ctx *c, const char *who, const void *rows, u64 row_cap
 }  // namespace khi
 using namespace khi;
 
-extern "C" int kh_unitigs_begin(kh_ctx *c, uint64_t min_count, uint64_t *n_unitigs, uint64_t *n_bases) {
+namespace khi {
+namespace {
+
+int unitigs_begin(kh_ctx *c, const char *who, uint64_t min_count, uint64_t *n_unitigs, uint64_t *n_bases, uint64_t *n_links, bool linked) {
     if (!c) return KH_ERR_BAD_ARG;
-    if (!n_unitigs || !n_bases) return fail(c, KH_ERR_BAD_ARG, "kh_unitigs_begin: NULL output");
+    if (!n_unitigs || !n_bases || (linked && !n_links)) return fail(c, KH_ERR_BAD_ARG, (std::string(who) + ": NULL output").c_str());
     *n_unitigs = *n_bases = 0;
-    if (c->shard_shift) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: the table is a shard; its k-mers' neighbours live on other owners");
+    if (linked) *n_links = 0;
+    if (c->shard_shift)
+        return fail(c, KH_ERR_STATE, (std::string(who) + ": the table is a shard; its k-mers' neighbours live on other owners").c_str());
     int rc = enter(c, true, true, false, true);  // as kh_result_sorted_device: the partition buffers are taken, a text stream ends
     if (rc != KH_OK) return rc;
     unitigs_release(c);
     const u64 mc = min_count ? min_count : 1;
     uint64_t n = 0;
     if ((rc = kh_result_size(c, mc, &n)) != KH_OK) return rc;
-    if (n > 0x7FFFFFFFull) return fail(c, KH_ERR_RANGE, "kh_unitigs_begin: more than 2^31 - 1 nodes: node ids are 32-bit");
+    if (n > 0x7FFFFFFFull) return fail(c, KH_ERR_RANGE, (std::string(who) + ": more than 2^31 - 1 nodes: node ids are 32-bit").c_str());
     if (n) {
         {
             SortScratch sc(c);
-            rc = unitigs_build(c, n, mc, sc);
+            rc = unitigs_build(c, n, mc, sc, linked);
             if (rc != KH_OK) (void)hipStreamSynchronize(c->stream);  // (before the scratch goes back)
         }
         if (rc != KH_OK) {
@@ -467,9 +626,51 @@ extern "C" int kh_unitigs_begin(kh_ctx *c, uint64_t min_count, uint64_t *n_uniti
         }
     }
     c->un.live = true;
+    c->un.linked = linked;
     *n_unitigs = c->un.n_unitigs;
     *n_bases = c->un.n_bases;
+    if (linked) *n_links = c->un.n_links;
     return KH_OK;
+}
+
+// What the two link copies check before they write anything.
+int links_copy_enter(kh_ctx *c, const char *who, const void *links, u64 cap) {
+    if (!c) return KH_ERR_BAD_ARG;
+    int rc = enter(c, true, true, false, true, true);  // a reader
+    if (rc != KH_OK) return rc;
+    if (!c->un.live)
+        return fail(c, KH_ERR_STATE,
+                    (std::string(who) + ": no unitigs: kh_unitigs_begin_linked first (anything that changes the table makes them stale)").c_str());
+    if (!c->un.linked) return fail(c, KH_ERR_STATE, (std::string(who) + ": no links were built: kh_unitigs_begin_linked, not kh_unitigs_begin").c_str());
+    if (cap && !links) return fail(c, KH_ERR_BAD_ARG, (std::string(who) + ": NULL array").c_str());
+    if ((links || cap) && cap < c->un.n_links) return fail(c, KH_ERR_RANGE, (std::string(who) + ": link array too small").c_str());
+    return KH_OK;
+}
+
+}  // namespace
+}  // namespace khi
+
+extern "C" int kh_unitigs_begin(kh_ctx *c, uint64_t min_count, uint64_t *n_unitigs, uint64_t *n_bases) {
+    return unitigs_begin(c, "kh_unitigs_begin", min_count, n_unitigs, n_bases, nullptr, false);
+}
+
+extern "C" int kh_unitigs_begin_linked(kh_ctx *c, uint64_t min_count, uint64_t *n_unitigs, uint64_t *n_bases, uint64_t *n_links) {
+    return unitigs_begin(c, "kh_unitigs_begin_linked", min_count, n_unitigs, n_bases, n_links, true);
+}
+
+extern "C" int kh_unitigs_links_copy_device(kh_ctx *c, uint64_t *d_links, uint64_t cap) {
+    int rc = links_copy_enter(c, "kh_unitigs_links_copy_device", d_links, cap);
+    if (rc != KH_OK) return rc;
+    if (d_links && c->un.n_links) HIP_TRY(c, hipMemcpyAsync(d_links, c->un.links, c->un.n_links * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return KH_OK;
+}
+
+extern "C" int kh_unitigs_links_copy(kh_ctx *c, uint64_t *links, uint64_t cap) {
+    int rc = links_copy_enter(c, "kh_unitigs_links_copy", links, cap);
+    if (rc != KH_OK) return rc;
+    if (links && c->un.n_links) rc = d2h_staged(c, links, c->un.links, c->un.n_links * sizeof(u64));
+    return rc;
 }
 
 extern "C" int kh_unitigs_copy_device(kh_ctx *c, uint64_t *d_rows, uint64_t row_cap, uint8_t *d_bases, uint64_t base_cap) {

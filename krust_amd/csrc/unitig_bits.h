@@ -1,5 +1,6 @@
 // unitig_bits.h -- the oriented-successor arithmetic of the unitig construction (include/kmerhip.h, "unitigs of a count table"),
-// shared by unitig.hip and by a plain host compiler (tests/unitig_bits_check.cpp compares it with string arithmetic for every k).
+// shared by unitig.hip and by a plain host compiler (tests/unitig_bits_check.cpp compares it with string arithmetic for every k,
+// tests/unitig_links_check.cpp the link word and the enter sign at the end of this file).
 //
 // An oriented node is (x, sign): sign 0 = (x, +) spells x's canonical string s, sign 1 = (x, -) spells rc(s).  As a state number it
 // is 2 * id + sign with id = the rank of x among the nodes, so rev() is ^ 1.
@@ -41,4 +42,21 @@ KH_HD bool kh_unitig_self_link(uint64_t x, uint64_t y) { return x == y; }
 // The ASCII letter at position i (0 = first) of a packed k-letter string.
 KH_HD uint8_t kh_unitig_letter(uint64_t w, uint32_t k, uint32_t i) {
     return (uint8_t)((0x54474341u >> (8u * (uint32_t)((w >> (2u * (k - 1u - i))) & 3u))) & 0xFFu);  // "ACGT"
+}
+
+// ---- links between unitigs (include/kmerhip.h, kh_unitigs_links_*) ----------------------------------------------------------
+// One word per link: 2 * from_unitig + from_sign in the high half, 2 * to_unitig + to_sign in the low half (+ = 0, - = 1).
+KH_HD uint64_t kh_unitig_link_word(uint32_t from, uint32_t from_sign, uint32_t to, uint32_t to_sign) {
+    return ((uint64_t)(2u * from + from_sign) << 32) | (uint64_t)(2u * to + to_sign);
+}
+
+#define KH_UNI_ENTER_NONE 2u  // the node entered lies at neither end of its unitig: never (include/kmerhip.h)
+
+// The sign a unitig of L nodes is entered with through the oriented node (y, ysign), y being the node at position pos of its
+// reported reading with sign rsign there: + if (y, ysign) is the reading's first oriented node, - if it is rev() of its last.
+// The first is tested first, so that a palindrome (L = 1, entered as + by kh_unitig_successor) is always entered as +.
+KH_HD uint32_t kh_unitig_enter_sign(uint32_t pos, uint32_t L, uint32_t rsign, uint32_t ysign) {
+    if (pos == 0u && ysign == rsign) return 0u;
+    if (pos + 1u == L && ysign != rsign) return 1u;
+    return KH_UNI_ENTER_NONE;
 }

@@ -29,6 +29,7 @@ static const char *USAGE =
     "                       [--min-count-a <N>] [--min-count-b <N>] [-m <MIN_COUNT>] [-f <FORMAT>] [--save <SAVE>] [--sorted] [-q]\n"
     "       kmerust graph <INDEX> [-m <MIN_COUNT>] [-f summary|tsv|json] [--sorted]\n"
     "       kmerust unitigs <INDEX> [-m <MIN_COUNT>] [-f fasta|summary]\n"
+    "       kmerust gfa <INDEX> [-m <MIN_COUNT>] [-f gfa|summary]\n"
     "\n"
     "Arguments:\n"
     "  <K>     K-mer length (1-32)\n"
@@ -75,6 +76,11 @@ static const char *USAGE =
     "unitigs: the maximal non-branching paths of that graph, built on the device, in ascending order of their first k-mers.\n"
     "  -f fasta (default)    >{i} LN:i:{bases} KC:i:{count sum} km:f:{mean count}, ' CR:i:1' on a circular one, then the sequence\n"
     "  -f summary            one {name}\\t{value} line each: unitigs, kmers, bases, circular, longest, n50\n"
+    "\n"
+    "gfa: those unitigs and the links between their ends, built on the device, as GFA 1.0.\n"
+    "  -f gfa (default)      H\\tVN:Z:1.0, then S\\t{i}\\t{sequence} with the tags of unitigs -f fasta, then per link, in ascending\n"
+    "                        order, L\\t{from}\\t{+|-}\\t{to}\\t{+|-}\\t{k-1}M\n"
+    "  -f summary            one {name}\\t{value} line each: unitigs, links, self_links, dead_ends, isolated, tips\n"
     "\n"
     "  -h, --help                         Print help\n"
     "  -V, --version                      Print version\n";
@@ -486,6 +492,51 @@ static int run_unitigs(int argc, char **argv) {
     return 0;
 }
 
+// kmerust gfa <INDEX> [-m N] [-f gfa|summary]: the unitigs of an index and the links between them (no reference counterpart)
+static int run_gfa(int argc, char **argv) {
+    std::string index;
+    bool have_index = false;
+    GfaFormat fmt = GfaFormat::Gfa;
+    uint64_t min_count = 1;
+    auto value_of = [&](int &i, const std::string &arg, const char *name) -> std::string {
+        const size_t eq = arg.find('=');
+        if (arg.rfind("--", 0) == 0 && eq != std::string::npos) return arg.substr(eq + 1);
+        if (arg.rfind("--", 0) != 0 && arg.size() > 2) return arg.substr(2);  // -fVALUE
+        if (i + 1 >= argc) usage_error(std::string("a value is required for '") + name + "' but none was supplied");
+        return argv[++i];
+    };
+    for (int i = 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        const std::string key = a.rfind("--", 0) == 0 ? a.substr(0, a.find('=')) : a.substr(0, 2);
+        if (key == "-f" || key == "--format") {
+            const std::string v = value_of(i, a, "--format <FORMAT>");
+            if (v == "gfa") fmt = GfaFormat::Gfa;
+            else if (v == "summary") fmt = GfaFormat::Summary;
+            else usage_error("invalid value '" + v + "' for '--format <FORMAT>'\n  [possible values: gfa, summary]");
+        } else if (key == "-m" || key == "--min-count") {
+            min_count = parse_u64(value_of(i, a, "--min-count <MIN_COUNT>"), "--min-count <MIN_COUNT>", UINT64_MAX);
+        } else if (a.size() > 1 && a[0] == '-' && a != "-") {
+            usage_error("unexpected argument '" + a + "' found");
+        } else if (!have_index) {
+            index = a;
+            have_index = true;
+        } else {
+            usage_error("unexpected argument '" + a + "' found");
+        }
+    }
+    if (!have_index) usage_error("the following required arguments were not provided:\n  <INDEX>\n\nUsage: kmerust gfa <INDEX>");
+#if !defined(__SANITIZE_ADDRESS__) && !defined(KMERUST_UNDER_ASAN) && !defined(KMERUST_ALWAYS_CLEAN_EXIT)  // (as cli_main)
+    leak_at_exit() = !getenv("KMERUST_CLEAN_EXIT");
+#endif
+    try {
+        gfa_index(index, min_count, fmt, stdout);
+    } catch (const Error &e) {
+        fprintf(stderr, "Application error:\n gfa: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 static int run_query(int argc, char **argv) {
     for (int i = 2; i < argc; ++i)
         if (!strncmp(argv[i], "--sequences", 11) && (argv[i][11] == 0 || argv[i][11] == '=')) return run_query_sequences(argc, argv);
@@ -556,6 +607,7 @@ int cli_main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "combine")) return run_two_indexes(argc, argv, true);
     if (argc > 1 && !strcmp(argv[1], "graph")) return run_graph(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "unitigs")) return run_unitigs(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "gfa")) return run_gfa(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "__parse")) return run_parse_dump(argc, argv);
 
     std::string k_arg, path = "-", save;

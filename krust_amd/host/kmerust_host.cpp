@@ -41,6 +41,10 @@
 #pragma weak kh_unitigs_copy_device
 #pragma weak kh_unitigs_copy
 #pragma weak kh_unitigs_end
+// ... and of `gfa`
+#pragma weak kh_unitigs_begin_linked
+#pragma weak kh_unitigs_links_copy_device
+#pragma weak kh_unitigs_links_copy
 
 namespace kmerust {
 
@@ -1406,6 +1410,58 @@ void unitigs_index(const std::string &index, uint64_t min_count, UnitigFormat fm
                 text.clear();
             }
         }
+    }
+    if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+}
+
+// =============================================================================================
+// the unitig graph of an index as GFA
+// =============================================================================================
+void write_link_summary(FILE *out, const LinkSummary &s) {
+    const std::pair<const char *, uint64_t> rows[] = {{"unitigs", s.unitigs},     {"links", s.links},       {"self_links", s.self_links},
+                                                      {"dead_ends", s.dead_ends}, {"isolated", s.isolated}, {"tips", s.tips}};
+    for (const auto &r : rows) fprintf(out, "%s\t%llu\n", r.first, (unsigned long long)r.second);
+}
+
+void gfa_index(const std::string &index, uint64_t min_count, GfaFormat fmt, FILE *out) {
+    if (!kh_unitigs_begin_linked || !kh_unitigs_links_copy || !kh_unitigs_links_copy_device || !kh_unitigs_copy || !kh_unitigs_end || !kh_merge_pairs)
+        throw Error("gfa needs a kmerhip library with kh_unitigs_begin_linked, kh_unitigs_links_copy, kh_unitigs_copy, kh_unitigs_end and kh_merge_pairs; the one this program was built against has neither");
+    PackedCounts idx = load_index(index);
+    const uint32_t k = idx.k;
+    IndexTable t(idx, -1);
+    idx = PackedCounts();  // (the host copy is no longer needed)
+    uint64_t nu = 0, nb = 0, nl = 0;
+    Session::check_on(t.c, kh_unitigs_begin_linked(t.c, min_count, &nu, &nb, &nl), "kh_unitigs_begin_linked");
+    std::vector<uint64_t> rows(nu * KH_UNI_WORDS), links(nl);
+    std::vector<uint8_t> bases(fmt == GfaFormat::Gfa ? nb : 0);
+    Session::check_on(t.c, kh_unitigs_copy(t.c, nu ? rows.data() : nullptr, nu ? nu : 0, bases.empty() ? nullptr : bases.data(), bases.size()), "kh_unitigs_copy");
+    Session::check_on(t.c, kh_unitigs_links_copy(t.c, nl ? links.data() : nullptr, nl), "kh_unitigs_links_copy");
+    Session::check_on(t.c, kh_unitigs_end(t.c), "kh_unitigs_end");
+    if (fmt == GfaFormat::Summary) {
+        write_link_summary(out, link_summary(rows.data(), nu, links.data(), nl, k));
+    } else {
+        std::string text = "H\tVN:Z:1.0\n";
+        auto flush = [&](bool last) {
+            if (text.size() >= (1u << 20) || last) {
+                if (fwrite(text.data(), 1, text.size(), out) != text.size()) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+                text.clear();
+            }
+        };
+        for (uint64_t i = 0; i < nu; ++i) {
+            const uint64_t *r = rows.data() + KH_UNI_WORDS * i;
+            const uint64_t start = r[KH_UNI_START], len = r[KH_UNI_KMERS] + k - 1;
+            if (start > nb || len > nb - start) throw Error("kh_unitigs_copy returned a row outside the bases");
+            text += gfa_segment_line(i, r, k, (const char *)bases.data() + start, len);
+            text.push_back('\n');
+            flush(false);
+        }
+        for (uint64_t j = 0; j < nl; ++j) {
+            if (KH_UNI_LINK_FROM(links[j]) >= nu || KH_UNI_LINK_TO(links[j]) >= nu) throw Error("kh_unitigs_links_copy returned a link outside the unitigs");
+            text += gfa_link_line(links[j], k);
+            text.push_back('\n');
+            flush(false);
+        }
+        flush(true);
     }
     if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
 }

@@ -360,6 +360,62 @@ void write_unitig_summary(FILE *out, const UnitigSummary &u);
 // kh_unitigs_* entry points.
 void unitigs_index(const std::string &index, uint64_t min_count, UnitigFormat fmt, FILE *out);
 
+// ---- the unitig graph of an index as GFA (`kmerust gfa`; no reference counterpart) ------------------------------------------------------
+// The tags of unitig_header() as GFA fields: "LN:i:{bases}\tKC:i:{count_sum}\tkm:f:{%.1f}" and "\tCR:i:1" behind them for a circular one.
+inline std::string gfa_segment_tags(const uint64_t *row, uint32_t k) {
+    const uint64_t L = row[KH_UNI_KMERS], cs = row[KH_UNI_COUNT_SUM];
+    char km[64];
+    snprintf(km, sizeof km, "%.1f", L ? (double)cs / (double)L : 0.0);
+    std::string t = "LN:i:" + std::to_string(L + k - 1) + "\tKC:i:" + std::to_string(cs) + "\tkm:f:" + km;
+    if (row[KH_UNI_FLAGS] & KH_UNI_CIRCULAR) t += "\tCR:i:1";
+    return t;
+}
+// The S line of unitig i, WITHOUT the newline: "S\t{i}\t{sequence}\t{tags}".  Pure.
+inline std::string gfa_segment_line(uint64_t i, const uint64_t *row, uint32_t k, const char *seq, size_t len) {
+    std::string s = "S\t" + std::to_string(i) + "\t";
+    s.append(seq, len);
+    s.push_back('\t');
+    s += gfa_segment_tags(row, k);
+    return s;
+}
+// The L line of a link word (include/kmerhip.h), WITHOUT the newline: "L\t{from}\t{+|-}\t{to}\t{+|-}\t{k-1}M".  Pure.
+inline std::string gfa_link_line(uint64_t w, uint32_t k) {
+    return "L\t" + std::to_string(KH_UNI_LINK_FROM(w)) + (KH_UNI_LINK_FROM_SIGN(w) ? "\t-\t" : "\t+\t") + std::to_string(KH_UNI_LINK_TO(w)) +
+           (KH_UNI_LINK_TO_SIGN(w) ? "\t-\t" : "\t+\t") + std::to_string(k - 1) + "M";
+}
+// What `kmerust gfa -f summary` derives from the n rows and the m link words: unitigs = n, links = m, self_links (from-unitig =
+// to-unitig), dead_ends (end states with no link out), isolated (unitigs with both ends dead) and tips (non-circular unitigs with
+// exactly one dead end and KMERS <= k).  A link whose from-unitig is not below n is not counted for any end.  Pure.
+struct LinkSummary {
+    uint64_t unitigs = 0, links = 0, self_links = 0, dead_ends = 0, isolated = 0, tips = 0;
+};
+inline LinkSummary link_summary(const uint64_t *rows, uint64_t n, const uint64_t *links, uint64_t m, uint32_t k) {
+    LinkSummary s;
+    s.unitigs = n;
+    s.links = m;
+    std::vector<uint8_t> out(n, 0);  // bit e: end e has a link out
+    for (uint64_t j = 0; j < m; ++j) {
+        const uint64_t from = KH_UNI_LINK_FROM(links[j]);
+        if (from == KH_UNI_LINK_TO(links[j])) ++s.self_links;
+        if (from < n) out[from] |= (uint8_t)(1u << KH_UNI_LINK_FROM_SIGN(links[j]));
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t *r = rows + KH_UNI_WORDS * i;
+        const unsigned dead = 2u - (out[i] & 1u) - ((out[i] >> 1) & 1u);
+        s.dead_ends += dead;
+        if (dead == 2) ++s.isolated;
+        if (dead == 1 && !(r[KH_UNI_FLAGS] & KH_UNI_CIRCULAR) && r[KH_UNI_KMERS] <= k) ++s.tips;
+    }
+    return s;
+}
+enum class GfaFormat { Gfa, Summary };
+// "{name}\t{value}" lines: unitigs, links, self_links, dead_ends, isolated, tips.
+void write_link_summary(FILE *out, const LinkSummary &s);
+// The index into a device table (as `unitigs` loads one), kh_unitigs_begin_linked / kh_unitigs_copy / kh_unitigs_links_copy /
+// kh_unitigs_end; Gfa: the header line, one S line per unitig, one L line per link in link order; Summary: link_summary.  Throws
+// Error -- also against a library without the kh_unitigs_begin_linked / kh_unitigs_links_copy entry points.
+void gfa_index(const std::string &index, uint64_t min_count, GfaFormat fmt, FILE *out);
+
 // ---- KMIX index (src/index.rs) -----------------------------------------------------------------
 uint32_t crc32_ieee(const uint8_t *data, size_t n, uint32_t crc = 0);  // src/index.rs:404-431
 void save_index(const PackedCounts &pc, const std::string &path);      // gzip if path ends in .gz

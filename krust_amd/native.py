@@ -54,6 +54,35 @@ def GRAPH_LEFT(c):
 UNI_WORDS, UNI_START, UNI_KMERS, UNI_COUNT_SUM, UNI_FLAGS = 4, 0, 1, 2, 3
 UNI_CIRCULAR = 1
 
+
+# KH_UNI_LINK_*: a link word of kh_unitigs_links_* -- 2 * from_unitig + from_sign above 2 * to_unitig + to_sign, + = 0, - = 1
+def uni_link_word(frm, from_sign, to, to_sign):
+    return ((2 * int(frm) + int(from_sign)) << 32) | (2 * int(to) + int(to_sign))
+
+
+def uni_link_from(w):
+    return int(w) >> 33
+
+
+def uni_link_from_sign(w):
+    return (int(w) >> 32) & 1
+
+
+def uni_link_to(w):
+    return (int(w) & 0xFFFFFFFF) >> 1
+
+
+def uni_link_to_sign(w):
+    return int(w) & 1
+
+
+def uni_link_fields(links):
+    """The four columns (from, from_sign, to, to_sign) of an array of link words, as uint32 arrays."""
+    w = np.asarray(links, dtype=np.uint64)
+    hi, lo = (w >> np.uint64(32)).astype(np.uint32), (w & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    return hi >> 1, hi & 1, lo >> 1, lo & 1
+
+
 _SET_OPS = {"intersect": SET_INTERSECT, "union": SET_UNION, "subtract": SET_SUBTRACT, "count-subtract": SET_COUNT_SUBTRACT}
 _CALCS = {"min": CALC_MIN, "max": CALC_MAX, "sum": CALC_SUM, "left": CALC_LEFT, "right": CALC_RIGHT}
 
@@ -126,6 +155,9 @@ SYMBOLS = {
     "kh_unitigs_copy_device": (C.c_int, [_P, _P, _U64, _P, _U64]),
     "kh_unitigs_copy": (C.c_int, [_P, _P, _U64, _P, _U64]),
     "kh_unitigs_end": (C.c_int, [_P]),
+    "kh_unitigs_begin_linked": (C.c_int, [_P, _U64, _P, _P, _P]),
+    "kh_unitigs_links_copy_device": (C.c_int, [_P, _P, _U64]),
+    "kh_unitigs_links_copy": (C.c_int, [_P, _P, _U64]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
     "kh_set_shard": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "kh_set_region_window": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -560,6 +592,35 @@ class DeviceCounter:
         nu, nb = self.unitigs_begin(min_count)
         try:
             return self.unitigs_copy(nu, nb)
+        finally:
+            self.unitigs_end()
+
+    # -- links between unitigs: the edges of the compacted graph -------------
+    def unitigs_begin_linked(self, min_count=1):
+        """kh_unitigs_begin_linked: unitigs_begin plus the links between the unitigs' ends; returns (n_unitigs, n_bases, n_links).
+        unitigs_copy* and unitigs_links_copy* fetch them, unitigs_end releases all of it."""
+        nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().kh_unitigs_begin_linked(self._h, int(min_count), C.byref(nu), C.byref(nb), C.byref(nl)))
+        return int(nu.value), int(nb.value), int(nl.value)
+
+    def unitigs_links_copy(self, n_links):
+        """kh_unitigs_links_copy into a fresh uint64 array: one word per link, ascending (uni_link_* take a word apart)."""
+        links = np.zeros(int(n_links), dtype=np.uint64)
+        self._check(lib().kh_unitigs_links_copy(self._h, links.ctypes.data if links.size else None, links.size))
+        return links
+
+    def unitigs_links_copy_device(self, d_links, cap):
+        """The same into device memory: an integer address or a torch tensor, 8-byte aligned, with room for cap words.  Returns
+        when it is complete."""
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        self._check(lib().kh_unitigs_links_copy_device(self._h, ptr(d_links), int(cap)))
+
+    def unitigs_linked(self, min_count=1):
+        """(rows, bases, links) of the unitigs of S and the links between their ends: begin, copy, end."""
+        nu, nb, nl = self.unitigs_begin_linked(min_count)
+        try:
+            rows, bases = self.unitigs_copy(nu, nb)
+            return rows, bases, self.unitigs_links_copy(nl)
         finally:
             self.unitigs_end()
 

@@ -6,6 +6,9 @@
 Per size: a k = 21 table from synthetic 150 bp reads of one seed (kh_synth_reads_device).  Every figure is the median of 5 runs
 after one warm call, with the spread (max - min) of the five beside it:
   unitigs_begin        kh_unitigs_begin(1): sort, ids, links, chain ranking, emit -- also as nodes / s
+  unitigs_begin_linked kh_unitigs_begin_linked(1): the same plus the links between the unitigs (end degrees, scan, link words);
+                       links_share = the part of its median that is not unitigs_begin's; n_links beside it
+  unitigs_links_copy   kh_unitigs_links_copy into a host array (8 bytes per link over the link)
   unitigs_copy_device  kh_unitigs_copy_device into device arrays (nothing crosses the link)
   unitigs_copy         kh_unitigs_copy into host arrays (32 bytes per unitig and one per base over the link)
   result_sorted_device the sort alone, begin's first step
@@ -53,6 +56,19 @@ def measure_one(n, k):
     out.update(nodes=nodes, unitigs=nu, bases=nb)
     rate = lambda r: dict(r, nodes_per_s=nodes / r["median_s"])
     out["unitigs_begin"] = rate(timed(lambda: a.unitigs_begin(1)))
+    linked = timed(lambda: a.unitigs_begin_linked(1))
+    nu2, nb2, nl = a.unitigs_begin_linked(1)
+    assert (nu2, nb2) == (nu, nb)
+    out["unitigs_begin_linked"] = dict(rate(linked), links_share=max(linked["median_s"] - out["unitigs_begin"]["median_s"], 0.0) / linked["median_s"])
+    out["n_links"] = nl
+    got_links = {}
+
+    def copy_links():
+        got_links["links"] = a.unitigs_links_copy(nl)
+
+    out["unitigs_links_copy"] = timed(copy_links)
+    links = got_links["links"]
+    assert links.size == nl and (links[1:] > links[:-1]).all()
     d_rows = torch.empty(max(4 * nu, 1), dtype=torch.int64, device="cuda:0")
     d_bases = torch.empty(max(nb, 1), dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
