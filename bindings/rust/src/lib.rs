@@ -128,6 +128,9 @@ pub mod sys {
         pub fn kh_unitigs_begin_linked(ctx: *mut KhCtx, min_count: u64, n_unitigs: *mut u64, n_bases: *mut u64, n_links: *mut u64) -> c_int;
         pub fn kh_unitigs_links_copy_device(ctx: *mut KhCtx, d_links: *mut u64, cap: u64) -> c_int;
         pub fn kh_unitigs_links_copy(ctx: *mut KhCtx, links: *mut u64, cap: u64) -> c_int;
+        /// one round of tip clipping of `src`'s compacted graph at `min_count`: the k-mers of the surviving unitigs are added to `dst`
+        /// (`count[key] += c`); `out` takes the 8 words KH_CLIP_* of the header names
+        pub fn kh_clip_tips_into(dst: *mut KhCtx, src: *mut KhCtx, min_count: u64, max_kmers: u64, out: *mut u64) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
         pub fn kh_result_sorted(ctx: *mut KhCtx, keys: *mut u64, counts: *mut u64, cap: u64,
                                 min_count: u64, n: *mut u64) -> c_int;
@@ -224,6 +227,18 @@ pub const fn uni_link_from_sign(w: u64) -> u32 { ((w >> 32) & 1) as u32 }
 pub const fn uni_link_to(w: u64) -> u32 { ((w & 0xFFFF_FFFF) >> 1) as u32 }
 /// `KH_UNI_LINK_TO_SIGN(w)`: 0 = entered at the start of its reported sequence (+), 1 = at the start of its reverse complement (-).
 pub const fn uni_link_to_sign(w: u64) -> u32 { (w & 1) as u32 }
+
+/// `KH_CLIP_WORDS`: the words of [`HipKmerMap::clip_tips_into`] -- unitigs, candidates, clipped, clipped_kmers, clipped_count,
+/// kept_kmers, kept_count, links (`CLIP_UNITIGS` .. `CLIP_LINKS`).
+pub const CLIP_WORDS: usize = 8;
+pub const CLIP_UNITIGS: usize = 0;
+pub const CLIP_CANDIDATES: usize = 1;
+pub const CLIP_CLIPPED: usize = 2;
+pub const CLIP_CLIPPED_KMERS: usize = 3;
+pub const CLIP_CLIPPED_COUNT: usize = 4;
+pub const CLIP_KEPT_KMERS: usize = 5;
+pub const CLIP_KEPT_COUNT: usize = 6;
+pub const CLIP_LINKS: usize = 7;
 
 /// KH_SET_*: the set operation of `kh_combine_into`.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -527,6 +542,18 @@ impl HipKmerMap {
         check(self.ctx, rc)?;
         check(self.ctx, end)?;
         Ok((rows, bases))
+    }
+
+    /// One round of tip clipping (`kh_clip_tips_into`): the unitigs and links of `src` at `min_count` are built on the device, a
+    /// non-circular unitig of at most `max_kmers` k-mers with exactly one dead end is clipped when at every link out of its attached
+    /// end a rival beats it (a unitig that is no candidate, or a candidate with the greater (KMERS, COUNT_SUM), then the smaller
+    /// index), and the k-mers of every surviving unitig are added to THIS table with their counts from `src` (`count[key] += c`).
+    /// `src` is only read; unitigs it had begun are released.  The borrow rules keep this table from being `src`.  Returns the
+    /// eight words ([`CLIP_UNITIGS`] .. [`CLIP_LINKS`]).
+    pub fn clip_tips_into(&mut self, src: &HipKmerMap, min_count: u64, max_kmers: u64) -> Result<[u64; CLIP_WORDS], HipError> {
+        let mut out = [0u64; CLIP_WORDS];
+        check(self.ctx, unsafe { sys::kh_clip_tips_into(self.ctx, src.ctx, min_count, max_kmers, out.as_mut_ptr()) })?;
+        Ok(out)
     }
 
     /// [`unitigs`](Self::unitigs) and the links between the unitigs' ends (`kh_unitigs_begin_linked` / `kh_unitigs_copy` /

@@ -478,6 +478,43 @@ int kh_unitigs_begin_linked(kh_ctx *ctx, uint64_t min_count, uint64_t *n_unitigs
 int kh_unitigs_links_copy_device(kh_ctx *ctx, uint64_t *d_links, uint64_t cap);
 int kh_unitigs_links_copy(kh_ctx *ctx, uint64_t *links, uint64_t cap);
 
+/* ---- tip clipping: one round of removing short dead-end branches (what assemblers do first with the compacted graph) --- */
+/* Take the unitigs and links of kh_unitigs_begin_linked(src, min_count): rows, end states (i, +) and (i, -) and link words exactly
+ * as defined above.  out(i, s) is the set of links whose from-state is (i, s).
+ * CANDIDATE: unitig i is a candidate when it is not KH_UNI_CIRCULAR, KMERS <= max_kmers, exactly one of out(i, +) and out(i, -)
+ *   is empty -- that end is the dead end, the other the ATTACHED end a_i --, and no link of out(a_i) goes to unitig i itself
+ *   (with either sign).
+ * RIVALS of a link a_i -> (j, t): the unitig indices b of all links (j, 1 - t) -> (b, sb).  By the mirror property of the link
+ *   list these are the unitigs that enter (j, t), and i is always among them (the device tests it all the same; a failure is
+ *   KH_ERR_STATE "internal error").  The sign of a palindromic unitig does not matter here: only indices are compared.
+ * BEATS: b beats i when b is no candidate, or b is a candidate and (KMERS_b, COUNT_SUM_b) is lexicographically greater than
+ *   (KMERS_i, COUNT_SUM_i), or the two are equal and b < i.  COUNT_SUM is the row's word as stored, modulo 2^64.
+ * CLIPPED: a candidate i is clipped when, at EVERY link of out(a_i), some rival b != i beats it.  All other unitigs survive.
+ * One call is one round: it decides from the graph as built, nothing cascades inside it.  A fork of two short dead ends loses
+ *   the weaker one; a short dead end beside a long branch, or beside one that continues, is lost; a short piece with two dead
+ *   ends or with none is not touched.
+ * RESULT: every k-mer of every surviving unitig is added to dst with its count from src -- count += c, exactly as
+ *   kh_merge_pairs_device does: a fresh or kh_reset dst ends up holding S minus the clipped k-mers.  K-mers of src below
+ *   min_count are not in S and are not copied.  max_kmers == 0 makes nothing a candidate: dst receives S.
+ * src is entered as kh_unitigs_begin_linked enters it (pending pushes are counted first, the table is read in the form it is
+ *   in, a text stream in progress ends, the partition buffers serve as scratch, a shard is KH_ERR_STATE, more than 2^31 - 1 nodes
+ *   is KH_ERR_RANGE); its table, counts and kh_stats are unchanged.  Any unitigs src had begun are RELEASED: afterwards
+ *   kh_unitigs_copy* and kh_unitigs_links_copy* on src are KH_ERR_STATE until the next begin.  dst is entered as kh_combine_into
+ *   enters its target.  dst == src, a NULL src or a NULL out is KH_ERR_BAD_ARG; different k or different devices are
+ *   KH_ERR_BAD_ARG, different shard states KH_ERR_STATE, as for kh_combine_into; every such refusal leaves both contexts usable.
+ *   No memory for the call's scratch is KH_ERR_OOM with src usable and dst holding what it held.  An empty S is KH_OK with all
+ *   words 0.  The error text is on dst. */
+#define KH_CLIP_WORDS 8
+#define KH_CLIP_UNITIGS 0         /* unitigs of src at min_count */
+#define KH_CLIP_CANDIDATES 1
+#define KH_CLIP_CLIPPED 2         /* unitigs clipped */
+#define KH_CLIP_CLIPPED_KMERS 3   /* sum of their KMERS */
+#define KH_CLIP_CLIPPED_COUNT 4   /* sum of their COUNT_SUM, modulo 2^64 */
+#define KH_CLIP_KEPT_KMERS 5      /* pairs added to dst */
+#define KH_CLIP_KEPT_COUNT 6      /* sum of their counts, modulo 2^64 */
+#define KH_CLIP_LINKS 7           /* links of src's compacted graph */
+int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out /* KH_CLIP_WORDS, host */);
+
 /* ---- multi-GPU merge (no reference counterpart) ----------- */
 /* Owner shard of a packed canonical k-mer among nparts shards: a fast-range of the top bits of
  * the table hash, so a shard is a contiguous range of table regions (same function on host and

@@ -467,6 +467,9 @@ struct SortScratch {
     void *take(u64 bytes);
 };
 int sorted_into(kh_ctx *c, u64 *out_keys, u64 *out_counts, u64 n, u64 min_count, SortScratch &sc);
+// ---- join.hip
+// What the table-against-table calls refuse before they enter anything (b, dst may be nullptr): `err` takes the text.
+int join_check(kh_ctx *err, const char *who, const kh_ctx *a, const kh_ctx *b, const kh_ctx *dst);
 // ---- unitig.hip
 void unitigs_release(kh_ctx *c);  // kh_unitigs_end / kh_reset / kh_destroy: the rows, bases and links of the last kh_unitigs_begin[_linked]
 // ---- profile.hip

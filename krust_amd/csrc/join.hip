@@ -147,6 +147,22 @@ __global__ __launch_bounds__(BLOCK) void join_kernel(SRC src, u64 s0, u64 s1, u6
 }  // namespace kh
 
 namespace khi {
+
+// What both calls refuse before they enter anything: `err` takes the text.
+int join_check(kh_ctx *err, const char *who, const kh_ctx *a, const kh_ctx *b, const kh_ctx *dst) {
+    const kh_ctx *all[3] = {a, b, dst};
+    std::string w = who;
+    for (const kh_ctx *x : all) {
+        if (!x) continue;
+        if (x->k != a->k) return fail(err, KH_ERR_BAD_ARG, (w + ": the contexts have different k").c_str());
+        if (x->device != a->device) return fail(err, KH_ERR_BAD_ARG, (w + ": the contexts are on different devices").c_str());
+    }
+    for (const kh_ctx *x : all)
+        if (x && (x->shard_shift != a->shard_shift || x->shard_index != a->shard_index))
+            return fail(err, KH_ERR_STATE, (w + ": the contexts are not in the same shard state").c_str());
+    return KH_OK;
+}
+
 namespace {
 
 constexpr u64 JOIN_WORDS = KH_CMP_WORDS + 1;  // the words of kh_compare, then the pair count of kh_combine_into
@@ -184,21 +200,6 @@ int join_launch(kh_ctx *on, const kh_ctx *src, u64 s0, u64 s1, u64 min_src, cons
     if (src->narrow) with_probe(kh::JsNarrow{(const u64 *)src->ntab, src->narrow_g});
     else with_probe(kh::JsWide{(const Slot *)src->table});
     HIP_TRY(on, hipGetLastError());
-    return KH_OK;
-}
-
-// What both calls refuse before they enter anything: `err` takes the text.
-int join_check(kh_ctx *err, const char *who, const kh_ctx *a, const kh_ctx *b, const kh_ctx *dst) {
-    const kh_ctx *all[3] = {a, b, dst};
-    std::string w = who;
-    for (const kh_ctx *x : all) {
-        if (!x) continue;
-        if (x->k != a->k) return fail(err, KH_ERR_BAD_ARG, (w + ": the contexts have different k").c_str());
-        if (x->device != a->device) return fail(err, KH_ERR_BAD_ARG, (w + ": the contexts are on different devices").c_str());
-    }
-    for (const kh_ctx *x : all)
-        if (x && (x->shard_shift != a->shard_shift || x->shard_index != a->shard_index))
-            return fail(err, KH_ERR_STATE, (w + ": the contexts are not in the same shard state").c_str());
     return KH_OK;
 }
 

@@ -27,6 +27,11 @@
 //   device_scan                degrees -> offsets; their sum is the number of links
 //   unitig_link_out_kernel<PRB> per end state: its up to four successors, four first-slot loads in flight, slot -> node id -> unitig,
 //                              position and sign in the reading -> link words, sorted in registers, stored at the lane's offset (no atomics)
+// kh_clip_tips_into only, behind the links and while the same scratch is live (one round of tip clipping, include/kmerhip.h):
+//   clip_candidate_kernel      per unitig: its row, the offsets of its two end states and the links of the attached end -> one byte
+//   clip_decide_kernel         per candidate: its links, the links out of each entered state reversed (the rivals), their bytes and
+//                              rows -> one clipped byte; six of the eight words by wave reductions
+//   clip_keep_kernel           per node in unitig order: a node of a surviving unitig is upserted into the OTHER context's table
 // No kernel waits for another workgroup, and no device loop is without a bound.  Rates were not measured (profiles/README.md r13).
 #include "ctx.hip.h"
 #include "probe.hip.h"
@@ -406,6 +411,155 @@ __global__ __launch_bounds__(BLOCK) void unitig_link_out_kernel(const u64 *__res
     }
 }
 
+// ---- tip clipping (kh_clip_tips_into) -----------------------------------------------------------------------------------------
+// The links of end state t = 2 i + s are links[loff[t] .. loff[t + 1]): the array is sorted by from-state.
+// Per unitig: 0 = no candidate, 1 = candidate attached at its + end, 2 = at its - end (the rule: include/kmerhip.h).  No probes.
+// kernel-resource-usage (gfx950, hipcc -O3): 22 VGPRs, 48 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void clip_candidate_kernel(u64 nu, u64 nl, u64 max_kmers, const u64 *__restrict__ rows, const u64 *__restrict__ loff,
+                                                               const u64 *__restrict__ links, uint8_t *__restrict__ cand, uint32_t *__restrict__ err) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < nu; i += (u64)gridDim.x * BLOCK) {
+        const u64 kmers = rows[KH_UNI_WORDS * i + KH_UNI_KMERS], flags = rows[KH_UNI_WORDS * i + KH_UNI_FLAGS];
+        const u64 o0 = loff[2 * i], o1 = loff[2 * i + 1], o2 = loff[2 * i + 2];
+        const u64 dp = o1 - o0, dm = o2 - o1;
+        uint32_t c = 0;
+        if (o0 > o1 || o1 > o2 || o2 > nl || dp > 4 || dm > 4) {
+            *err = 1u;
+        } else if (!(flags & KH_UNI_CIRCULAR) && kmers <= max_kmers && (dp == 0) != (dm == 0)) {
+            const uint32_t s = dp ? 0u : 1u;
+            const u64 a0 = s ? o1 : o0, d = s ? dm : dp;
+            bool self = false;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j)
+                if (j < d && KH_UNI_LINK_TO(links[a0 + j]) == (uint32_t)i) self = true;
+            c = self ? 0u : 1u + s;
+        }
+        cand[i] = (uint8_t)c;
+    }
+}
+
+// Per candidate: its up to four links, for each the up to four links out of the state it enters, reversed -- the rivals --, their
+// candidate bytes and rows (kh_clip_beats) -> one clipped byte.  The four second-level offset pairs are loaded before any is
+// used.  The first six words of kh_clip_tips_into: per-lane sums, one reduction per wave and word, one atomic by its lane 0.
+// kernel-resource-usage (gfx950, hipcc -O3): 51 VGPRs, 90 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void clip_decide_kernel(u64 nu, u64 nl, const u64 *__restrict__ rows, const u64 *__restrict__ loff,
+                                                            const u64 *__restrict__ links, const uint8_t *__restrict__ cand,
+                                                            uint8_t *__restrict__ clipped, uint32_t *__restrict__ err, u64 *__restrict__ words) {
+    u64 s_uni = 0, s_links = 0, s_cand = 0, s_clip = 0, s_kmers = 0, s_count = 0;
+    bool bad = false;
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < nu; i += (u64)gridDim.x * BLOCK) {
+        const uint32_t ci = cand[i];
+        s_uni += 1;
+        s_links += loff[2 * i + 2] - loff[2 * i];
+        uint32_t cl = 0;
+        if (ci) {
+            const u64 ti = 2 * i + (ci - 1u);
+            const u64 a0 = loff[ti];
+            u64 d = loff[ti + 1] - a0;
+            if (d < 1 || d > 4 || a0 + d > nl) {  // (never: clip_candidate_kernel saw the same offsets)
+                bad = true;
+                d = 0;
+            }
+            const u64 ki = rows[KH_UNI_WORDS * i + KH_UNI_KMERS], si = rows[KH_UNI_WORDS * i + KH_UNI_COUNT_SUM];
+            u64 tt[4], lo[4], hi[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                tt[j] = ti;  // (a state that is there: the loads below need no branch)
+                if (j < d) {
+                    const u64 t = (links[a0 + j] & 0xFFFFFFFFull) ^ 1ull;  // (j, 1 - t): the entered state, reversed
+                    if (t < 2 * nu) tt[j] = t;
+                    else bad = true;
+                }
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) lo[j] = loff[tt[j]];  // (all four offset pairs in flight)
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) hi[j] = loff[tt[j] + 1];
+            bool all = d > 0;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                if (j >= d) continue;
+                u64 e = hi[j] - lo[j];
+                if (lo[j] > hi[j] || e > 4 || hi[j] > nl) {
+                    bad = true;
+                    e = 0;
+                }
+                bool found = false, beaten = false;
+#pragma unroll
+                for (uint32_t m = 0; m < 4; ++m) {
+                    if (m >= e) continue;
+                    const uint32_t b = KH_UNI_LINK_TO(links[lo[j] + m]);
+                    if (b == (uint32_t)i) {
+                        found = true;
+                    } else if (b < nu) {
+                        const bool cb = cand[b] != 0;
+                        if (!cb || kh_clip_beats(rows[KH_UNI_WORDS * (u64)b + KH_UNI_KMERS], rows[KH_UNI_WORDS * (u64)b + KH_UNI_COUNT_SUM], b, true, ki, si,
+                                                 (uint32_t)i))
+                            beaten = true;
+                    } else {
+                        bad = true;
+                    }
+                }
+                if (!found) bad = true;  // i is not among its own rivals
+                all = all && beaten;
+            }
+            cl = all ? 1u : 0u;
+            s_cand += 1;
+            if (cl) {
+                s_clip += 1;
+                s_kmers += ki;
+                s_count += si;
+            }
+        }
+        clipped[i] = (uint8_t)cl;
+    }
+    if (kh_any(bad) && lane_id() == 0) *err = 1u;
+    s_uni = wave_sum(s_uni);
+    s_links = wave_sum(s_links);
+    s_cand = wave_sum(s_cand);
+    s_clip = wave_sum(s_clip);
+    s_kmers = wave_sum(s_kmers);
+    s_count = wave_sum(s_count);
+    if (lane_id() == 0) {
+        if (s_uni) atomicAdd(&words[KH_CLIP_UNITIGS], s_uni);
+        if (s_links) atomicAdd(&words[KH_CLIP_LINKS], s_links);
+        if (s_cand) atomicAdd(&words[KH_CLIP_CANDIDATES], s_cand);
+        if (s_clip) atomicAdd(&words[KH_CLIP_CLIPPED], s_clip);
+        if (s_kmers) atomicAdd(&words[KH_CLIP_CLIPPED_KMERS], s_kmers);
+        if (s_count) atomicAdd(&words[KH_CLIP_CLIPPED_COUNT], s_count);
+    }
+}
+
+// Nodes [q0, q1) of the unitig order: a node of a surviving unitig hands (keys[id], counts[id]) to the target table, count += c
+// as table_merge_pairs_kernel, whose counters it keeps; the two kept words as above.
+// kernel-resource-usage (gfx950, hipcc -O3): 33 VGPRs, 73 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void clip_keep_kernel(TableGeom tg, u64 q0, u64 q1, uint32_t n, u64 nu, const uint32_t *__restrict__ order,
+                                                          const uint32_t *__restrict__ ordu, const uint8_t *__restrict__ clipped,
+                                                          const u64 *__restrict__ keys, const u64 *__restrict__ counts, Counters *ctr,
+                                                          u64 *__restrict__ words) {
+    uint32_t nd = 0, nf = 0;
+    u64 ad = 0, np = 0;
+    for (u64 q = q0 + (u64)blockIdx.x * BLOCK + threadIdx.x; q < q1; q += (u64)gridDim.x * BLOCK) {
+        const uint32_t u = ordu[q], id = order[q] & ~UNI_SIGN;
+        if (u >= nu || id >= n || clipped[u]) continue;
+        const u64 key = keys[id], c = counts[id];
+        if (key != KH_EMPTY_KEY && c != 0) {
+            upsert(tg, key, c, nd, nf);
+            ad += c;
+            np += 1;
+        }
+    }
+    const u64 d = wave_sum((u64)nd), f = wave_sum((u64)nf);
+    ad = wave_sum(ad);
+    np = wave_sum(np);
+    if (lane_id() == 0) {
+        if (d) atomicAdd(&ctr->distinct, d);
+        if (f) atomicAdd(&ctr->failed, f);
+        if (ad) atomicAdd(&ctr->kmers, ad);
+        if (np) atomicAdd(&words[KH_CLIP_KEPT_KMERS], np);
+        if (ad) atomicAdd(&words[KH_CLIP_KEPT_COUNT], ad);
+    }
+}
+
 }  // namespace kh
 
 namespace khi {
@@ -450,8 +604,61 @@ int unitig_rank(kh_ctx *c, const uint32_t *next, u64 states, kh::UniRank *cur, k
     return KH_OK;
 }
 
+// kh_clip_tips_into: the target and the rule's bound in, the eight words out.
+struct ClipJob {
+    kh_ctx *dst;
+    u64 max_kmers;
+    u64 words[KH_CLIP_WORDS];
+    bool on_dst;  // a failure came from dst's side: its text is there already
+};
+
+// One round of tip clipping behind the links of c, while unitigs_build's scratch is live: the two decision kernels on c's stream,
+// then the surviving nodes into job->dst on ITS stream, in ranges it has room for (as combine_scan of join.hip).  Every failure
+// before the first insert leaves dst as it was.
+int clip_step(kh_ctx *c, ClipJob *job, SortScratch &sc, u64 n, u64 nu, u64 nl, const u64 *keys, const u64 *counts, const uint32_t *order,
+              const uint32_t *ordu, const u64 *loff, uint32_t *d_err) {
+    kh_ctx *const dst = job->dst;
+    uint8_t *const cand = (uint8_t *)sc.take(nu);
+    uint8_t *const clipped = (uint8_t *)sc.take(nu);
+    u64 *const words = (u64 *)sc.take(KH_CLIP_WORDS * sizeof(u64));
+    if (!cand || !clipped || !words) return soft_oom(c, "device memory for the tip clipping's scratch");
+    HIP_TRY(c, hipMemsetAsync(words, 0, KH_CLIP_WORDS * sizeof(u64), c->stream));
+    hipLaunchKernelGGL(kh::clip_candidate_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, job->max_kmers, (const u64 *)c->un.rows, loff,
+                       (const u64 *)c->un.links, cand, d_err);
+    hipLaunchKernelGGL(kh::clip_decide_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, (const u64 *)c->un.rows, loff,
+                       (const u64 *)c->un.links, (const uint8_t *)cand, clipped, d_err, words);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t bad = 0;
+    HIP_TRY(c, hipMemcpyAsync(&bad, d_err, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(job->words, words, sizeof(job->words), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the clipped bytes are complete: dst's stream may read them)
+    if (bad || job->words[KH_CLIP_UNITIGS] != nu || job->words[KH_CLIP_LINKS] != nl)
+        return fail(c, KH_ERR_STATE, "kh_clip_tips_into: a candidate is not among its own rivals, or the links do not add up (internal error)");
+    int rc = KH_OK;
+    job->on_dst = true;
+    const u64 step = SUB_TILES * kh::TILE;
+    for (u64 q0 = 0; q0 < n && rc == KH_OK;) {
+        const u64 m = std::min(step, n - q0);
+        bool smaller = false;
+        if ((rc = ensure_room(dst, m, false, &smaller)) != KH_OK) break;
+        hipLaunchKernelGGL(kh::clip_keep_kernel, dim3(uni_grid(m)), dim3(kh::BLOCK), 0, dst->stream, table_geom(dst, dst->table, dst->cap), q0, q0 + m,
+                           (uint32_t)n, nu, order, ordu, (const uint8_t *)clipped, keys, counts, dst->d_ctr, words);
+        if (hipGetLastError() != hipSuccess) rc = fail(dst, KH_ERR_HIP, "clip_keep_kernel");
+        dst->table_empty = false;
+        dst->rheads_valid = false;
+        dst->pending_bound += m;
+        q0 += m;
+    }
+    if (rc == KH_OK && hipMemcpyAsync(job->words + KH_CLIP_KEPT_KMERS, words + KH_CLIP_KEPT_KMERS, 2 * sizeof(u64), hipMemcpyDeviceToHost, dst->stream) != hipSuccess)
+        rc = fail(dst, KH_ERR_HIP, "kh_clip_tips_into: the kept words");
+    if (rc == KH_OK) rc = sync_counters(dst);  // (complete when it returns; an upsert without a free slot shows here)
+    else (void)hipStreamSynchronize(dst->stream);  // (before the scratch goes back)
+    return rc;
+}
+
 // linked: kh_unitigs_begin_linked -- the link array behind the same kernels; nothing of it is launched or allocated without.
-int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked) {
+// clip: kh_clip_tips_into -- linked, without the base array, and clip_step() behind the links.
+int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJob *clip = nullptr) {
     const uint32_t n32 = (uint32_t)n, k = c->k;
     const u64 states = 2 * n;
     u64 *const keys = (u64 *)sc.take(n * sizeof(u64));
@@ -522,7 +729,7 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked) {
     HIP_TRY(c, hipMemcpyAsync(&nb, ustart + nu, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (nb != n + nu * (k - 1)) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: the unitigs' lengths do not add up (internal error)");
-    if (hipMalloc((void **)&c->un.bases, nb) != hipSuccess) {
+    if (!clip && hipMalloc((void **)&c->un.bases, nb) != hipSuccess) {
         (void)hipGetLastError();
         c->un.bases = nullptr;
         return soft_oom(c, "hipMalloc(unitig bases)");
@@ -531,8 +738,9 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked) {
                        (const u64 *)uidx, (const u64 *)ustart, nu, order, ordu, c->un.rows, d_flag + 1);
     hipLaunchKernelGGL(kh::unitig_sum_kernel, dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, n32, (const uint32_t *)order, (const uint32_t *)ordu,
                        (const u64 *)counts, nu, c->un.rows);
-    hipLaunchKernelGGL(kh::unitig_bases_kernel, dim3(uni_grid((nb + 15) / 16)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k,
-                       (const uint32_t *)order, (const u64 *)ustart, nu, nb, c->un.bases);
+    if (!clip)
+        hipLaunchKernelGGL(kh::unitig_bases_kernel, dim3(uni_grid((nb + 15) / 16)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k,
+                           (const uint32_t *)order, (const u64 *)ustart, nu, nb, c->un.bases);
     HIP_TRY(c, hipGetLastError());
     // the links: every end state's out-degree -> offsets; their sum comes back with the consistency word
     uint32_t *deg = nullptr;
@@ -577,6 +785,7 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked) {
     c->un.n_unitigs = nu;
     c->un.n_bases = nb;
     c->un.n_links = nl;
+    if (clip) return clip_step(c, clip, sc, n, nu, nl, keys, counts, order, ordu, loff, d_flag + 1);
     return KH_OK;
 }
 
@@ -656,6 +865,43 @@ extern "C" int kh_unitigs_begin(kh_ctx *c, uint64_t min_count, uint64_t *n_uniti
 
 extern "C" int kh_unitigs_begin_linked(kh_ctx *c, uint64_t min_count, uint64_t *n_unitigs, uint64_t *n_bases, uint64_t *n_links) {
     return unitigs_begin(c, "kh_unitigs_begin_linked", min_count, n_unitigs, n_bases, n_links, true);
+}
+
+// src's unitigs and links are built as kh_unitigs_begin_linked builds them (without the bases), decided and handed on while the
+// scratch is live, and released again: nothing of them outlives the call.
+extern "C" int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out) {
+    if (!dst) return KH_ERR_BAD_ARG;
+    if (!src || !out) return fail(dst, KH_ERR_BAD_ARG, "kh_clip_tips_into: NULL argument");
+    if (dst == src) return fail(dst, KH_ERR_BAD_ARG, "kh_clip_tips_into: dst must not be src");
+    int rc = join_check(dst, "kh_clip_tips_into", src, nullptr, dst);
+    if (rc != KH_OK) return rc;
+    if (src->shard_shift) return fail(dst, KH_ERR_STATE, "kh_clip_tips_into: the table is a shard; its k-mers' neighbours live on other owners");
+    auto from_src = [&](int r) {  // (the error text is on dst)
+        if (r != KH_OK) dst->last_error = src->last_error;
+        return r;
+    };
+    if ((rc = enter(src, true, true, false, true)) != KH_OK) return from_src(rc);  // as kh_unitigs_begin_linked
+    unitigs_release(src);
+    if ((rc = enter(dst)) != KH_OK) return rc;  // as kh_combine_into
+    const u64 mc = min_count ? min_count : 1;
+    uint64_t n = 0;
+    if ((rc = kh_result_size(src, mc, &n)) != KH_OK) return from_src(rc);
+    if (n > 0x7FFFFFFFull) return fail(dst, KH_ERR_RANGE, "kh_clip_tips_into: more than 2^31 - 1 nodes: node ids are 32-bit");
+    ClipJob job{dst, max_kmers, {0, 0, 0, 0, 0, 0, 0, 0}, false};
+    if (n) {
+        {
+            SortScratch sc(src);
+            rc = unitigs_build(src, n, mc, sc, true, &job);
+            if (rc != KH_OK) {
+                (void)hipStreamSynchronize(src->stream);  // (before the scratch goes back)
+                (void)hipStreamSynchronize(dst->stream);
+            }
+        }
+        unitigs_release(src);
+        if (rc != KH_OK) return job.on_dst ? rc : from_src(rc);
+    }
+    memcpy(out, job.words, sizeof(job.words));
+    return KH_OK;
 }
 
 extern "C" int kh_unitigs_links_copy_device(kh_ctx *c, uint64_t *d_links, uint64_t cap) {

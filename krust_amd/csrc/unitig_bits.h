@@ -1,6 +1,6 @@
 // unitig_bits.h -- the oriented-successor arithmetic of the unitig construction (include/kmerhip.h, "unitigs of a count table"),
 // shared by unitig.hip and by a plain host compiler (tests/unitig_bits_check.cpp compares it with string arithmetic for every k,
-// tests/unitig_links_check.cpp the link word and the enter sign at the end of this file).
+// tests/unitig_links_check.cpp the link word and the enter sign, tests/clip_bits_check.cpp the tip-clipping comparator at the end of this file).
 //
 // An oriented node is (x, sign): sign 0 = (x, +) spells x's canonical string s, sign 1 = (x, -) spells rc(s).  As a state number it
 // is 2 * id + sign with id = the rank of x among the nodes, so rev() is ^ 1.
@@ -59,4 +59,14 @@ KH_HD uint32_t kh_unitig_enter_sign(uint32_t pos, uint32_t L, uint32_t rsign, ui
     if (pos == 0u && ysign == rsign) return 0u;
     if (pos + 1u == L && ysign != rsign) return 1u;
     return KH_UNI_ENTER_NONE;
+}
+
+// ---- tip clipping (include/kmerhip.h, kh_clip_tips_into; tests/clip_bits_check.cpp) -------------------------------------------------
+// Whether rival b beats candidate i (b != i): any unitig that is no candidate does; a candidate does by the greater
+// (KMERS, COUNT_SUM), the sum as the row stores it, and at a tie by the smaller index.
+KH_HD bool kh_clip_beats(uint64_t kmers_b, uint64_t sum_b, uint32_t idx_b, bool cand_b, uint64_t kmers_i, uint64_t sum_i, uint32_t idx_i) {
+    if (!cand_b) return true;
+    if (kmers_b != kmers_i) return kmers_b > kmers_i;
+    if (sum_b != sum_i) return sum_b > sum_i;
+    return idx_b < idx_i;
 }

@@ -30,6 +30,7 @@ static const char *USAGE =
     "       kmerust graph <INDEX> [-m <MIN_COUNT>] [-f summary|tsv|json] [--sorted]\n"
     "       kmerust unitigs <INDEX> [-m <MIN_COUNT>] [-f fasta|summary]\n"
     "       kmerust gfa <INDEX> [-m <MIN_COUNT>] [-f gfa|summary]\n"
+    "       kmerust clip <INDEX> [-m <MIN_COUNT>] [--max-kmers <L>] [--rounds <R>] [-f <FORMAT>] [--save <SAVE>] [--sorted] [-q]\n"
     "\n"
     "Arguments:\n"
     "  <K>     K-mer length (1-32)\n"
@@ -81,6 +82,13 @@ static const char *USAGE =
     "  -f gfa (default)      H\\tVN:Z:1.0, then S\\t{i}\\t{sequence} with the tags of unitigs -f fasta, then per link, in ascending\n"
     "                        order, L\\t{from}\\t{+|-}\\t{to}\\t{+|-}\\t{k-1}M\n"
     "  -f summary            one {name}\\t{value} line each: unitigs, links, self_links, dead_ends, isolated, tips\n"
+    "\n"
+    "clip: tip clipping of that graph on the device, written like a count (-f, -m, --save, --sorted): a unitig of at most L k-mers\n"
+    "  with exactly one dead end goes when, at every link out of its other end, a longer or better covered branch enters the same\n"
+    "  place.  One round decides from the graph as it is; the k-mers of the surviving unitigs are the next round's index.\n"
+    "      --max-kmers <L>                The longest unitig, in k-mers, that can be clipped [default: k]\n"
+    "      --rounds <R>                   Rounds to run at most; 0: until a round clips nothing [default: 1]\n"
+    "  stderr, unless -q: round\\tunitigs\\tcandidates\\tclipped\\tclipped_kmers\\tkept_kmers, one line per round\n"
     "\n"
     "  -h, --help                         Print help\n"
     "  -V, --version                      Print version\n";
@@ -537,6 +545,25 @@ static int run_gfa(int argc, char **argv) {
     return 0;
 }
 
+// kmerust clip <INDEX> [-m N] [--max-kmers L] [--rounds R] [-f FORMAT] [--sorted] [--save OUT] [-q]: tip clipping of an index's unitig
+// graph (no reference counterpart)
+static int run_clip(int argc, char **argv) {
+    const ClipArgs args = parse_clip_args(std::vector<std::string>(argv + 2, argv + argc));
+    if (!args.error.empty()) usage_error(args.error);
+#if !defined(__SANITIZE_ADDRESS__) && !defined(KMERUST_UNDER_ASAN) && !defined(KMERUST_ALWAYS_CLEAN_EXIT)  // (as cli_main)
+    leak_at_exit() = !getenv("KMERUST_CLEAN_EXIT");
+#endif
+    try {
+        uint64_t n = 0;
+        clip_index(args, stdout, args.quiet ? nullptr : stderr, args.save.empty() ? nullptr : &n);
+        if (!args.quiet && !args.save.empty()) fprintf(stderr, "saved: %s (%llu k-mers)\n", args.save.c_str(), (unsigned long long)n);
+    } catch (const Error &e) {
+        fprintf(stderr, "Application error:\n clip: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 static int run_query(int argc, char **argv) {
     for (int i = 2; i < argc; ++i)
         if (!strncmp(argv[i], "--sequences", 11) && (argv[i][11] == 0 || argv[i][11] == '=')) return run_query_sequences(argc, argv);
@@ -608,6 +635,7 @@ int cli_main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "graph")) return run_graph(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "unitigs")) return run_unitigs(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "gfa")) return run_gfa(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "clip")) return run_clip(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "__parse")) return run_parse_dump(argc, argv);
 
     std::string k_arg, path = "-", save;

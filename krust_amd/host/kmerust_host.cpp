@@ -45,6 +45,8 @@
 #pragma weak kh_unitigs_begin_linked
 #pragma weak kh_unitigs_links_copy_device
 #pragma weak kh_unitigs_links_copy
+// ... and of `clip`
+#pragma weak kh_clip_tips_into
 
 namespace kmerust {
 
@@ -1310,6 +1312,50 @@ void combine_indexes(uint32_t op, uint32_t calc, const std::string &index_a, con
     if (fmt == OutputFormat::Histogram) write_histogram(out, s.histogram(min_count));
     else if (s.device_text_ok(fmt)) s.write_text(out, fmt, min_count);
     else write_counts(out, s.result(min_count), fmt, 1);
+}
+
+// =============================================================================================
+// tip clipping of an index's unitig graph
+// =============================================================================================
+void clip_index(const ClipArgs &args, FILE *out, FILE *log, uint64_t *n_pairs) {
+    if (!kh_clip_tips_into || !kh_merge_pairs)
+        throw Error("clip needs a kmerhip library with kh_clip_tips_into and kh_merge_pairs; the one this program was built against has neither");
+    PackedCounts idx = load_index(args.index);
+    const uint32_t k = idx.k;
+    const uint64_t n0 = idx.keys.size();
+    IndexTable t(idx, -1);
+    idx = PackedCounts();  // (the host copy is no longer needed)
+    KmerCounter kc;
+    kc.k(k).capacity_hint(n0).sorted(args.sorted);
+    Session a(kc, false), b(kc, false);
+    Session *into = &a, *other = &b;
+    kh_ctx *from = t.c;
+    const uint64_t max_kmers = args.have_max_kmers ? args.max_kmers : k;
+    if (log) fputs("round\tunitigs\tcandidates\tclipped\tclipped_kmers\tkept_kmers\n", log);
+    for (uint64_t round = 1;; ++round) {
+        uint64_t words[KH_CLIP_WORDS];
+        into->check(kh_clip_tips_into(into->ctx, from, args.min_count, max_kmers, words), "kh_clip_tips_into");
+        if (log) fputs(clip_round_line(round, words).c_str(), log);
+        Session::check_on(from, kh_reset(from), "kh_reset");
+        if (clip_stops(round, args.rounds, words[KH_CLIP_CLIPPED])) break;
+        from = into->ctx;
+        std::swap(into, other);
+    }
+    Session &s = *into;
+    if (!args.save.empty() || n_pairs) {  // as `combine --save`: the index holds ALL pairs, the output honours min_count
+        const PackedCounts all = s.result(1);
+        if (n_pairs) *n_pairs = all.keys.size();
+        if (!args.save.empty()) {
+            save_index(all, args.save);
+            if (args.format == OutputFormat::Histogram || !s.device_text_ok(args.format)) {
+                write_counts(out, all, args.format, args.min_count);
+                return;
+            }
+        }
+    }
+    if (args.format == OutputFormat::Histogram) write_histogram(out, s.histogram(args.min_count));
+    else if (s.device_text_ok(args.format)) s.write_text(out, args.format, args.min_count);
+    else write_counts(out, s.result(args.min_count), args.format, 1);
 }
 
 // =============================================================================================

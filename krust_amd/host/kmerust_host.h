@@ -416,6 +416,91 @@ void write_link_summary(FILE *out, const LinkSummary &s);
 // Error -- also against a library without the kh_unitigs_begin_linked / kh_unitigs_links_copy entry points.
 void gfa_index(const std::string &index, uint64_t min_count, GfaFormat fmt, FILE *out);
 
+// ---- tip clipping of an index's unitig graph (`kmerust clip`; no reference counterpart) -------------------------------------------------
+// kmerust clip <INDEX> [-m N] [--max-kmers L] [--rounds R] [-f fasta|tsv|json|histogram] [--sorted] [--save OUT] [-q]
+// What the arguments behind "clip" say.  `error` is empty, or the text of a usage error (what follows "error: ").  Pure.
+struct ClipArgs {
+    std::string index, save, error;
+    bool have_index = false, have_max_kmers = false, sorted = false, quiet = false;
+    uint64_t min_count = 1, max_kmers = 0, rounds = 1;  // max_kmers without --max-kmers: k, which the index says; rounds 0: until nothing is clipped
+    OutputFormat format = OutputFormat::Fasta;
+};
+// "invalid digit found in string" / "number too large to fit in target type", as the other sub-commands say it; empty when *v is set
+inline std::string clip_parse_u64(const std::string &s, const char *what, uint64_t *v) {
+    if (s.empty() || s.find_first_not_of("0123456789") != std::string::npos || s.size() > 20)
+        return "invalid value '" + s + "' for '" + what + "': invalid digit found in string";
+    uint64_t x = 0;
+    for (char ch : s) {
+        const uint64_t d = (uint64_t)(ch - '0');
+        if (x > (UINT64_MAX - d) / 10) return "invalid value '" + s + "' for '" + what + "': number too large to fit in target type";
+        x = x * 10 + d;
+    }
+    *v = x;
+    return "";
+}
+// args: what follows "kmerust clip" on the command line
+inline ClipArgs parse_clip_args(const std::vector<std::string> &args) {
+    ClipArgs c;
+    size_t i = 0;
+    auto value_of = [&](const std::string &arg, const char *name, std::string *v) {
+        const size_t eq = arg.find('=');
+        if (arg.rfind("--", 0) == 0 && eq != std::string::npos) *v = arg.substr(eq + 1);
+        else if (arg.rfind("--", 0) != 0 && arg.size() > 2) *v = arg.substr(2);  // -fVALUE
+        else if (i + 1 >= args.size()) c.error = std::string("a value is required for '") + name + "' but none was supplied";
+        else *v = args[++i];
+        return c.error.empty();
+    };
+    for (; i < args.size() && c.error.empty(); ++i) {
+        const std::string &a = args[i];
+        const std::string key = a.rfind("--", 0) == 0 ? a.substr(0, a.find('=')) : a.substr(0, 2);
+        std::string v;
+        if (a == "-q" || a == "--quiet") {
+            c.quiet = true;
+        } else if (a == "--sorted") {
+            c.sorted = true;
+        } else if (key == "-f" || key == "--format") {
+            if (!value_of(a, "--format <FORMAT>", &v)) break;
+            if (v == "fasta") c.format = OutputFormat::Fasta;
+            else if (v == "tsv") c.format = OutputFormat::Tsv;
+            else if (v == "json") c.format = OutputFormat::Json;
+            else if (v == "histogram") c.format = OutputFormat::Histogram;
+            else c.error = "invalid value '" + v + "' for '--format <FORMAT>'\n  [possible values: fasta, tsv, json, histogram]";
+        } else if (key == "-m" || key == "--min-count") {
+            if (value_of(a, "--min-count <MIN_COUNT>", &v)) c.error = clip_parse_u64(v, "--min-count <MIN_COUNT>", &c.min_count);
+        } else if (key == "--max-kmers") {
+            if (value_of(a, "--max-kmers <L>", &v)) c.error = clip_parse_u64(v, "--max-kmers <L>", &c.max_kmers);
+            c.have_max_kmers = c.error.empty();
+        } else if (key == "--rounds") {
+            if (value_of(a, "--rounds <R>", &v)) c.error = clip_parse_u64(v, "--rounds <R>", &c.rounds);
+        } else if (key == "--save") {
+            value_of(a, "--save <SAVE>", &c.save);
+        } else if (a.size() > 1 && a[0] == '-' && a != "-") {
+            c.error = "unexpected argument '" + a + "' found";
+        } else if (!c.have_index) {
+            c.index = a;
+            c.have_index = true;
+        } else {
+            c.error = "unexpected argument '" + a + "' found";
+        }
+    }
+    if (c.error.empty() && !c.have_index) c.error = "the following required arguments were not provided:\n  <INDEX>\n\nUsage: kmerust clip <INDEX>";
+    return c;
+}
+// Whether the loop ends behind a round: it clipped nothing, or `limit` rounds have run (limit 0: no limit).  Pure.
+inline bool clip_stops(uint64_t rounds_done, uint64_t limit, uint64_t clipped) { return clipped == 0 || (limit != 0 && rounds_done >= limit); }
+// The stderr line of round `round` (from 1), WITH the newline, from the KH_CLIP_WORDS words of kh_clip_tips_into:
+// "{round}\t{unitigs}\t{candidates}\t{clipped}\t{clipped_kmers}\t{kept_kmers}\n".  Pure.
+inline std::string clip_round_line(uint64_t round, const uint64_t *words) {
+    return std::to_string(round) + "\t" + std::to_string(words[KH_CLIP_UNITIGS]) + "\t" + std::to_string(words[KH_CLIP_CANDIDATES]) + "\t" +
+           std::to_string(words[KH_CLIP_CLIPPED]) + "\t" + std::to_string(words[KH_CLIP_CLIPPED_KMERS]) + "\t" + std::to_string(words[KH_CLIP_KEPT_KMERS]) +
+           "\n";
+}
+// The index into a device table (as `unitigs` loads one), then rounds between two further contexts: kh_clip_tips_into, kh_reset of the
+// table just read, swap -- until clip_stops().  The last table through the writers of `combine` (format, min_count, sorted, save).
+// log (unless NULL): the header line "round\tunitigs\tcandidates\tclipped\tclipped_kmers\tkept_kmers" and one clip_round_line per round.
+// *n_pairs (optional): the pairs of the last table.  Throws Error -- also against a library without kh_clip_tips_into.
+void clip_index(const ClipArgs &args, FILE *out, FILE *log, uint64_t *n_pairs = nullptr);
+
 // ---- KMIX index (src/index.rs) -----------------------------------------------------------------
 uint32_t crc32_ieee(const uint8_t *data, size_t n, uint32_t crc = 0);  // src/index.rs:404-431
 void save_index(const PackedCounts &pc, const std::string &path);      // gzip if path ends in .gz

@@ -83,6 +83,12 @@ def uni_link_fields(links):
     return hi >> 1, hi & 1, lo >> 1, lo & 1
 
 
+# KH_CLIP_*: the words of kh_clip_tips_into
+CLIP_WORDS = 8
+CLIP_UNITIGS, CLIP_CANDIDATES, CLIP_CLIPPED, CLIP_CLIPPED_KMERS, CLIP_CLIPPED_COUNT, CLIP_KEPT_KMERS, CLIP_KEPT_COUNT, CLIP_LINKS = range(8)
+CLIP_NAMES = ("unitigs", "candidates", "clipped", "clipped_kmers", "clipped_count", "kept_kmers", "kept_count", "links")
+
+
 _SET_OPS = {"intersect": SET_INTERSECT, "union": SET_UNION, "subtract": SET_SUBTRACT, "count-subtract": SET_COUNT_SUBTRACT}
 _CALCS = {"min": CALC_MIN, "max": CALC_MAX, "sum": CALC_SUM, "left": CALC_LEFT, "right": CALC_RIGHT}
 
@@ -158,6 +164,7 @@ SYMBOLS = {
     "kh_unitigs_begin_linked": (C.c_int, [_P, _U64, _P, _P, _P]),
     "kh_unitigs_links_copy_device": (C.c_int, [_P, _P, _U64]),
     "kh_unitigs_links_copy": (C.c_int, [_P, _P, _U64]),
+    "kh_clip_tips_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
     "kh_set_shard": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "kh_set_region_window": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -623,6 +630,18 @@ class DeviceCounter:
             return rows, bases, self.unitigs_links_copy(nl)
         finally:
             self.unitigs_end()
+
+    # -- tip clipping: one round over the compacted graph ---------------------
+    def clip_tips_into(self, src, min_count=1, max_kmers=None):
+        """kh_clip_tips_into: one round of tip clipping of `src`'s compacted graph at min_count -- the k-mers of every surviving
+        unitig are added to THIS table with their counts from src (count[key] += c).  A dead-end unitig of at most max_kmers
+        k-mers (None: k) is clipped when at every link out of its attached end a rival beats it (include/kmerhip.h).  src's
+        table is only read, unitigs it had begun are released; this table must not be src.  Returns the eight words as a dict:
+        unitigs, candidates, clipped, clipped_kmers, clipped_count, kept_kmers, kept_count, links."""
+        out = np.zeros(CLIP_WORDS, dtype=np.uint64)
+        mk = self.k if max_kmers is None else int(max_kmers)
+        self._check(lib().kh_clip_tips_into(self._h, src._h, int(min_count), mk, out.ctypes.data))
+        return dict(zip(CLIP_NAMES, (int(x) for x in out)))
 
     # -- multi-GPU merge ---------------------------------------------------
     def comm_init(self, nranks, rank, unique_id):

@@ -13,6 +13,10 @@ after one warm call, with the spread (max - min) of the five beside it:
   unitigs_copy         kh_unitigs_copy into host arrays (32 bytes per unitig and one per base over the link)
   result_sorted_device the sort alone, begin's first step
   graph_stats          kh_graph_stats(1): eight probes per node, as begin's index pass makes
+With --clip, per size and in one process, only these two, on the same table:
+  unitigs_begin_linked kh_unitigs_begin_linked(1), as above
+  clip_tips_into       kh_clip_tips_into(1, max_kmers = k) into a fresh context hinted with the node count, kh_reset (not timed)
+                       before every call; clip_share = the part of its median that is not unitigs_begin_linked's; the eight words beside it
 The measurement runs in a child process with a timeout; a failure is reported as {"error": ...}."""
 import argparse
 import json
@@ -96,8 +100,47 @@ def measure_one(n, k):
     return out
 
 
+def measure_clip_one(n, k):
+    import torch
+    from krust_amd import native
+    rl = 150
+    t = torch.empty(n * (rl + 1), dtype=torch.uint8, device="cuda:0")
+    native.synth_reads_device(t.data_ptr(), None, 20260130, 1 << 28, rl, 0, n, device=0)
+    torch.cuda.synchronize()
+    a = native.DeviceCounter(k, device=0)
+    a.push_device(t.data_ptr(), None, t.numel())
+    st = a.finish()
+    del t
+    out = {"k": k, "reads": n, "table": {f: st[f] for f in ("distinct", "kmers", "table_slots", "slot_bytes")}}
+    nodes = st["distinct"]
+    rate = lambda r: dict(r, nodes_per_s=nodes / r["median_s"])
+    linked = timed(lambda: a.unitigs_begin_linked(1))
+    a.unitigs_end()
+    out["unitigs_begin_linked"] = rate(linked)
+    b = native.DeviceCounter(k, device=0, capacity_hint=nodes)
+    got = {}
+    ts = []
+    for rep in range(6):                      # one warm call, then five
+        b.reset()
+        t0 = time.perf_counter()
+        got["words"] = b.clip_tips_into(a, 1, k)
+        ts.append(time.perf_counter() - t0)
+    ts = sorted(ts[1:])
+    clip = {"median_s": ts[len(ts) // 2], "spread_s": ts[-1] - ts[0]}
+    out["clip_tips_into"] = dict(rate(clip), clip_share=max(clip["median_s"] - linked["median_s"], 0.0) / clip["median_s"])
+    out["words"] = got["words"]
+    sb = b.finish()
+    assert sb["distinct"] == got["words"]["kept_kmers"] and sb["kmers"] == got["words"]["kept_count"]
+    assert got["words"]["kept_kmers"] + got["words"]["clipped_kmers"] == nodes and a.finish()["distinct"] == nodes
+    out["dst_grows"] = sb["grows"]
+    b.close()
+    a.close()
+    return out
+
+
 def measure(args):
-    print("RESULT " + json.dumps([measure_one(n, args.k) for n in args.reads]))
+    one = measure_clip_one if args.clip else measure_one
+    print("RESULT " + json.dumps([one(n, args.k) for n in args.reads]))
 
 
 def main():
@@ -105,19 +148,20 @@ def main():
     ap.add_argument("--reads", type=int, nargs="+", default=[1_000_000, 10_000_000])
     ap.add_argument("--k", type=int, default=21)
     ap.add_argument("--timeout", type=int, default=900)
+    ap.add_argument("--clip", action="store_true", help="kh_clip_tips_into beside kh_unitigs_begin_linked, nothing else")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
         measure(args)
         return
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k), "--reads"] + [str(n) for n in args.reads]
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k)] + (["--clip"] if args.clip else []) + ["--reads"] + [str(n) for n in args.reads]
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
         line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
         res = json.loads(line[-1][7:]) if p.returncode == 0 and line else {"error": f"exit {p.returncode}", "stderr": p.stderr[-2000:]}
     except subprocess.TimeoutExpired:
         res = {"error": f"no result within {args.timeout} s"}
-    print(json.dumps({"probe": "unitig", "result": res}, indent=1))
+    print(json.dumps({"probe": "unitig-clip" if args.clip else "unitig", "result": res}, indent=1))
 
 
 if __name__ == "__main__":
