@@ -1108,6 +1108,43 @@ struct OutBuf {
         fflush(out);
     }
 };
+
+// The same pieces for a writer that has to know: `text` is appended to by the caller and handed on by wrote() once it holds 1 MiB, and
+// by finish(), which also flushes the stream; a short write or a failed flush is an Error.  What is still in `text` when something
+// else throws is not written.
+struct CheckedOut {
+    FILE *out;
+    std::string text;
+    void wrote(bool last = false) {
+        if (text.size() < (1u << 20) && !last) return;
+        if (fwrite(text.data(), 1, text.size(), out) != text.size()) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+        text.clear();
+    }
+    void finish() {
+        wrote(true);
+        if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+    }
+};
+
+// The table of `s` written like a count (`combine`, `clip`): `save` (unless empty) takes ALL pairs as an index, `out` the records with
+// count >= min_count in format `fmt` -- the device text stream where the format has one --, in the order s.sorted says.  *n_pairs
+// (optional): all pairs of the table.
+void write_like_count(Session &s, OutputFormat fmt, uint64_t min_count, const std::string &save, FILE *out, uint64_t *n_pairs) {
+    if (!save.empty() || n_pairs) {  // as `kmerust --save`: the index holds ALL pairs, the output honours min_count
+        const PackedCounts all = s.result(1);
+        if (n_pairs) *n_pairs = all.keys.size();
+        if (!save.empty()) {
+            save_index(all, save);
+            if (fmt == OutputFormat::Histogram || !s.device_text_ok(fmt)) {
+                write_counts(out, all, fmt, min_count);
+                return;
+            }
+        }
+    }
+    if (fmt == OutputFormat::Histogram) write_histogram(out, s.histogram(min_count));
+    else if (s.device_text_ok(fmt)) s.write_text(out, fmt, min_count);
+    else write_counts(out, s.result(min_count), fmt, 1);
+}
 }  // namespace
 
 // =============================================================================================
@@ -1301,17 +1338,7 @@ void combine_indexes(uint32_t op, uint32_t calc, const std::string &index_a, con
     uint64_t n = 0;
     s.check(kh_combine_into(s.ctx, a.c, b.c, op, calc, min_a, min_b, &n), "kh_combine_into");
     if (n_pairs) *n_pairs = n;
-    if (!save.empty()) {  // as `kmerust --save`: the index holds ALL pairs, the output honours min_count
-        const PackedCounts all = s.result(1);
-        save_index(all, save);
-        if (fmt == OutputFormat::Histogram || !s.device_text_ok(fmt)) {
-            write_counts(out, all, fmt, min_count);
-            return;
-        }
-    }
-    if (fmt == OutputFormat::Histogram) write_histogram(out, s.histogram(min_count));
-    else if (s.device_text_ok(fmt)) s.write_text(out, fmt, min_count);
-    else write_counts(out, s.result(min_count), fmt, 1);
+    write_like_count(s, fmt, min_count, save, out, nullptr);
 }
 
 // =============================================================================================
@@ -1341,21 +1368,7 @@ void clip_index(const ClipArgs &args, FILE *out, FILE *log, uint64_t *n_pairs) {
         from = into->ctx;
         std::swap(into, other);
     }
-    Session &s = *into;
-    if (!args.save.empty() || n_pairs) {  // as `combine --save`: the index holds ALL pairs, the output honours min_count
-        const PackedCounts all = s.result(1);
-        if (n_pairs) *n_pairs = all.keys.size();
-        if (!args.save.empty()) {
-            save_index(all, args.save);
-            if (args.format == OutputFormat::Histogram || !s.device_text_ok(args.format)) {
-                write_counts(out, all, args.format, args.min_count);
-                return;
-            }
-        }
-    }
-    if (args.format == OutputFormat::Histogram) write_histogram(out, s.histogram(args.min_count));
-    else if (s.device_text_ok(args.format)) s.write_text(out, args.format, args.min_count);
-    else write_counts(out, s.result(args.min_count), args.format, 1);
+    write_like_count(*into, args.format, args.min_count, args.save, out, n_pairs);
 }
 
 // =============================================================================================
@@ -1383,6 +1396,7 @@ void graph_index(const std::string &index, uint64_t min_count, GraphFormat fmt, 
     const uint32_t k = idx.k;
     IndexTable t(idx, -1);
     idx = PackedCounts();  // (the host copy is no longer needed)
+    CheckedOut w{out, ""};
     if (fmt != GraphFormat::Tsv) {
         uint64_t words[KH_GRAPH_WORDS];
         Session::check_on(t.c, kh_graph_stats(t.c, min_count, words), "kh_graph_stats");
@@ -1405,16 +1419,12 @@ void graph_index(const std::string &index, uint64_t min_count, GraphFormat fmt, 
         if (sorted && !kh_result_sorted) sort_pairs(pc);
         std::vector<uint8_t> masks(got);
         Session::check_on(t.c, kh_graph_masks(t.c, pc.keys.data(), got, min_count, masks.data()), "kh_graph_masks");
-        std::string text;
         for (uint64_t i = 0; i < got; ++i) {
-            format_graph_line(text, pc.keys[i], k, pc.counts[i], masks[i]);
-            if (text.size() >= (1u << 20) || i + 1 == got) {
-                if (fwrite(text.data(), 1, text.size(), out) != text.size()) throw Error(std::string("failed to write output: ") + std::strerror(errno));
-                text.clear();
-            }
+            format_graph_line(w.text, pc.keys[i], k, pc.counts[i], masks[i]);
+            w.wrote();
         }
     }
-    if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+    w.finish();
 }
 
 // =============================================================================================
@@ -1439,25 +1449,22 @@ void unitigs_index(const std::string &index, uint64_t min_count, UnitigFormat fm
     std::vector<uint8_t> bases(fmt == UnitigFormat::Fasta ? nb : 0);
     Session::check_on(t.c, kh_unitigs_copy(t.c, nu ? rows.data() : nullptr, nu ? nu : 0, bases.empty() ? nullptr : bases.data(), bases.size()), "kh_unitigs_copy");
     Session::check_on(t.c, kh_unitigs_end(t.c), "kh_unitigs_end");
+    CheckedOut w{out, ""};
     if (fmt == UnitigFormat::Summary) {
         write_unitig_summary(out, unitig_summary(rows.data(), nu, k));
     } else {
-        std::string text;
         for (uint64_t i = 0; i < nu; ++i) {
             const uint64_t *r = rows.data() + KH_UNI_WORDS * i;
             const uint64_t start = r[KH_UNI_START], len = r[KH_UNI_KMERS] + k - 1;
             if (start > nb || len > nb - start) throw Error("kh_unitigs_copy returned a row outside the bases");
-            text += unitig_header(i, r, k);
-            text.push_back('\n');
-            text.append((const char *)bases.data() + start, len);
-            text.push_back('\n');
-            if (text.size() >= (1u << 20) || i + 1 == nu) {
-                if (fwrite(text.data(), 1, text.size(), out) != text.size()) throw Error(std::string("failed to write output: ") + std::strerror(errno));
-                text.clear();
-            }
+            w.text += unitig_header(i, r, k);
+            w.text.push_back('\n');
+            w.text.append((const char *)bases.data() + start, len);
+            w.text.push_back('\n');
+            w.wrote();
         }
     }
-    if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+    w.finish();
 }
 
 // =============================================================================================
@@ -1483,33 +1490,27 @@ void gfa_index(const std::string &index, uint64_t min_count, GfaFormat fmt, FILE
     Session::check_on(t.c, kh_unitigs_copy(t.c, nu ? rows.data() : nullptr, nu ? nu : 0, bases.empty() ? nullptr : bases.data(), bases.size()), "kh_unitigs_copy");
     Session::check_on(t.c, kh_unitigs_links_copy(t.c, nl ? links.data() : nullptr, nl), "kh_unitigs_links_copy");
     Session::check_on(t.c, kh_unitigs_end(t.c), "kh_unitigs_end");
+    CheckedOut w{out, ""};
     if (fmt == GfaFormat::Summary) {
         write_link_summary(out, link_summary(rows.data(), nu, links.data(), nl, k));
     } else {
-        std::string text = "H\tVN:Z:1.0\n";
-        auto flush = [&](bool last) {
-            if (text.size() >= (1u << 20) || last) {
-                if (fwrite(text.data(), 1, text.size(), out) != text.size()) throw Error(std::string("failed to write output: ") + std::strerror(errno));
-                text.clear();
-            }
-        };
+        w.text = "H\tVN:Z:1.0\n";
         for (uint64_t i = 0; i < nu; ++i) {
             const uint64_t *r = rows.data() + KH_UNI_WORDS * i;
             const uint64_t start = r[KH_UNI_START], len = r[KH_UNI_KMERS] + k - 1;
             if (start > nb || len > nb - start) throw Error("kh_unitigs_copy returned a row outside the bases");
-            text += gfa_segment_line(i, r, k, (const char *)bases.data() + start, len);
-            text.push_back('\n');
-            flush(false);
+            w.text += gfa_segment_line(i, r, k, (const char *)bases.data() + start, len);
+            w.text.push_back('\n');
+            w.wrote();
         }
         for (uint64_t j = 0; j < nl; ++j) {
             if (KH_UNI_LINK_FROM(links[j]) >= nu || KH_UNI_LINK_TO(links[j]) >= nu) throw Error("kh_unitigs_links_copy returned a link outside the unitigs");
-            text += gfa_link_line(links[j], k);
-            text.push_back('\n');
-            flush(false);
+            w.text += gfa_link_line(links[j], k);
+            w.text.push_back('\n');
+            w.wrote();
         }
-        flush(true);
     }
-    if (fflush(out) != 0) throw Error(std::string("failed to write output: ") + std::strerror(errno));
+    w.finish();
 }
 
 // =============================================================================================

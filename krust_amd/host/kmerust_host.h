@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <numeric>
@@ -26,6 +27,7 @@
 #include <vector>
 
 #include "../../include/kmerhip.h"
+#include "cli_args.h"
 
 namespace kmerust {
 
@@ -425,67 +427,8 @@ struct ClipArgs {
     uint64_t min_count = 1, max_kmers = 0, rounds = 1;  // max_kmers without --max-kmers: k, which the index says; rounds 0: until nothing is clipped
     OutputFormat format = OutputFormat::Fasta;
 };
-// "invalid digit found in string" / "number too large to fit in target type", as the other sub-commands say it; empty when *v is set
-inline std::string clip_parse_u64(const std::string &s, const char *what, uint64_t *v) {
-    if (s.empty() || s.find_first_not_of("0123456789") != std::string::npos || s.size() > 20)
-        return "invalid value '" + s + "' for '" + what + "': invalid digit found in string";
-    uint64_t x = 0;
-    for (char ch : s) {
-        const uint64_t d = (uint64_t)(ch - '0');
-        if (x > (UINT64_MAX - d) / 10) return "invalid value '" + s + "' for '" + what + "': number too large to fit in target type";
-        x = x * 10 + d;
-    }
-    *v = x;
-    return "";
-}
-// args: what follows "kmerust clip" on the command line
-inline ClipArgs parse_clip_args(const std::vector<std::string> &args) {
-    ClipArgs c;
-    size_t i = 0;
-    auto value_of = [&](const std::string &arg, const char *name, std::string *v) {
-        const size_t eq = arg.find('=');
-        if (arg.rfind("--", 0) == 0 && eq != std::string::npos) *v = arg.substr(eq + 1);
-        else if (arg.rfind("--", 0) != 0 && arg.size() > 2) *v = arg.substr(2);  // -fVALUE
-        else if (i + 1 >= args.size()) c.error = std::string("a value is required for '") + name + "' but none was supplied";
-        else *v = args[++i];
-        return c.error.empty();
-    };
-    for (; i < args.size() && c.error.empty(); ++i) {
-        const std::string &a = args[i];
-        const std::string key = a.rfind("--", 0) == 0 ? a.substr(0, a.find('=')) : a.substr(0, 2);
-        std::string v;
-        if (a == "-q" || a == "--quiet") {
-            c.quiet = true;
-        } else if (a == "--sorted") {
-            c.sorted = true;
-        } else if (key == "-f" || key == "--format") {
-            if (!value_of(a, "--format <FORMAT>", &v)) break;
-            if (v == "fasta") c.format = OutputFormat::Fasta;
-            else if (v == "tsv") c.format = OutputFormat::Tsv;
-            else if (v == "json") c.format = OutputFormat::Json;
-            else if (v == "histogram") c.format = OutputFormat::Histogram;
-            else c.error = "invalid value '" + v + "' for '--format <FORMAT>'\n  [possible values: fasta, tsv, json, histogram]";
-        } else if (key == "-m" || key == "--min-count") {
-            if (value_of(a, "--min-count <MIN_COUNT>", &v)) c.error = clip_parse_u64(v, "--min-count <MIN_COUNT>", &c.min_count);
-        } else if (key == "--max-kmers") {
-            if (value_of(a, "--max-kmers <L>", &v)) c.error = clip_parse_u64(v, "--max-kmers <L>", &c.max_kmers);
-            c.have_max_kmers = c.error.empty();
-        } else if (key == "--rounds") {
-            if (value_of(a, "--rounds <R>", &v)) c.error = clip_parse_u64(v, "--rounds <R>", &c.rounds);
-        } else if (key == "--save") {
-            value_of(a, "--save <SAVE>", &c.save);
-        } else if (a.size() > 1 && a[0] == '-' && a != "-") {
-            c.error = "unexpected argument '" + a + "' found";
-        } else if (!c.have_index) {
-            c.index = a;
-            c.have_index = true;
-        } else {
-            c.error = "unexpected argument '" + a + "' found";
-        }
-    }
-    if (c.error.empty() && !c.have_index) c.error = "the following required arguments were not provided:\n  <INDEX>\n\nUsage: kmerust clip <INDEX>";
-    return c;
-}
+// args: what follows "kmerust clip" on the command line (with the other commands' parsers, below)
+inline ClipArgs parse_clip_args(const std::vector<std::string> &args);
 // Whether the loop ends behind a round: it clipped nothing, or `limit` rounds have run (limit 0: no limit).  Pure.
 inline bool clip_stops(uint64_t rounds_done, uint64_t limit, uint64_t clipped) { return clipped == 0 || (limit != 0 && rounds_done >= limit); }
 // The stderr line of round `round` (from 1), WITH the newline, from the KH_CLIP_WORDS words of kh_clip_tips_into:
@@ -508,5 +451,237 @@ PackedCounts load_index(const std::string &path);                      // valida
 
 // ---- CLI ---------------------------------------------------------------------------------------
 int cli_main(int argc, char **argv);
+
+// What the arguments of each command say (src/cli.rs:33-144 for the counting command; the sub-commands have no reference
+// counterpart).  Every parse_*_args takes what follows the command's word on the command line and is pure (cli_args.h): `error` is
+// empty, or the text of the usage error.  A list of spellings is in the order of the enum or the KH_* constants it stands for.
+inline const Choices OUTPUT_FORMATS = {"fasta", "tsv", "json", "histogram"};
+inline const Choices INPUT_FORMATS = {"auto", "fasta", "fastq"};
+inline const Choices PROFILE_FORMATS = {"summary", "profile"};
+inline const Choices COMPARE_FORMATS = {"tsv", "json"};
+inline const Choices GRAPH_FORMATS = {"summary", "tsv", "json"};
+inline const Choices UNITIG_FORMATS = {"fasta", "summary"};
+inline const Choices GFA_FORMATS = {"gfa", "summary"};
+inline const Choices CALCS = {"min", "max", "sum", "left", "right"};                  // KH_CALC_*: position + 1
+inline const Choices SET_OPS = {"intersect", "union", "subtract", "count-subtract"};  // KH_SET_*: position + 1
+static_assert(KH_CALC_MIN == 1 && KH_CALC_SUM == 3 && KH_CALC_RIGHT == 5 && KH_SET_INTERSECT == 1 && KH_SET_COUNT_SUBTRACT == 4,
+              "CALCS and SET_OPS are in the order of the constants");
+
+// parse_k, src/cli.rs:103-114 (to: size_t)
+inline std::string check_k(const std::string &s, const std::string &what, void *to) {
+    uint64_t k = 0;
+    if (s.size() > 19 || !parse_u64(s, what, UINT64_MAX, &k).empty()) return invalid_value(s, what, ": '" + s + "' is not a valid number");
+    if (k == 0) return invalid_value(s, what, ": k-mer length must be at least 1");
+    if (k > 32) return invalid_value(s, what, ": k-mer length must be at most 32");
+    *static_cast<size_t *>(to) = (size_t)k;
+    return "";
+}
+// --min-fraction (to: double)
+inline std::string check_fraction(const std::string &v, const std::string &what, void *to) {
+    char *end = nullptr;
+    const double f = v.empty() ? -1.0 : strtod(v.c_str(), &end);
+    if (v.empty() || *end || v.find_first_not_of("0123456789.eE+-") != std::string::npos) return invalid_value(v, what, ": invalid float literal");
+    if (!(f >= 0.0 && f <= 1.0)) return invalid_value(v, what, ": must be between 0 and 1");
+    *static_cast<double *>(to) = f;
+    return "";
+}
+// --gpus N: the ordinals 0 .. N-1; --devices a,b,c: those (to: std::vector<int>; the later of the two options wins)
+inline std::string check_gpus(const std::string &v, const std::string &what, void *to) {
+    uint64_t n = 0;
+    const std::string err = parse_u64(v, what, 64, &n);
+    if (!err.empty()) return err;
+    if (n == 0) return invalid_value("0", what, ": at least one GPU is needed");
+    std::vector<int> &devices = *static_cast<std::vector<int> *>(to);
+    devices.clear();
+    for (uint64_t d = 0; d < n; ++d) devices.push_back((int)d);
+    return "";
+}
+inline std::string check_devices(const std::string &v, const std::string &what, void *to) {
+    std::vector<int> devices;
+    for (size_t pos = 0; pos <= v.size();) {
+        const size_t comma = std::min(v.find(',', pos), v.size());
+        uint64_t d = 0;
+        const std::string err = parse_u64(v.substr(pos, comma - pos), what, 1023, &d);
+        if (!err.empty()) return err;
+        devices.push_back((int)d);
+        pos = comma + 1;
+    }
+    *static_cast<std::vector<int> *>(to) = devices;
+    return "";
+}
+
+// kmerust [OPTIONS] <K> [PATH]
+struct CountArgs {
+    std::string error, path = "-", save;
+    bool help = false, version = false;  // -h / -V: the walk ended there, and nothing behind it was looked at
+    bool quiet = false, sorted = false;
+    size_t k = 0;
+    OutputFormat format = OutputFormat::Fasta;
+    SequenceFormat input_format = SequenceFormat::Auto;
+    uint64_t min_count = 1;
+    int min_quality = -1;      // -1: none
+    std::vector<int> devices;  // extension: several GPUs (no counterpart in src/cli.rs)
+};
+inline CountArgs parse_count_args(const std::vector<std::string> &args) {
+    CountArgs c;
+    size_t fmt = 0, in_fmt = 0;
+    uint64_t quality = 0;
+    bool have_quality = false;
+    std::vector<std::string> pos;
+    const Command cmd = {{flag("-h", "--help", &c.help, true), flag("-V", "--version", &c.version, true), flag("-q", "--quiet", &c.quiet),
+                          choice("-f", "--format", "<FORMAT>", OUTPUT_FORMATS, &fmt), choice("-i", "--input-format", "<INPUT_FORMAT>", INPUT_FORMATS, &in_fmt),
+                          number("-m", "--min-count", "<MIN_COUNT>", &c.min_count), number("-Q", "--min-quality", "<MIN_QUALITY>", &quality, 255, &have_quality),
+                          text(nullptr, "--save", "<SAVE>", &c.save), flag(nullptr, "--sorted", &c.sorted),
+                          custom(nullptr, "--gpus", "<N>", check_gpus, &c.devices), custom(nullptr, "--devices", "<LIST>", check_devices, &c.devices)},
+                         {"<K>", "[PATH]"}, 1, "Usage: kmerust <K> [PATH]"};
+    c.error = parse_args(cmd, args, &pos);
+    if (c.help || c.version) return c;
+    if (c.error.empty()) c.error = missing_args(cmd, pos);
+    if (c.error.empty()) c.error = check_k(pos[0], "<K>", &c.k);
+    if (pos.size() > 1) c.path = pos[1];
+    c.format = (OutputFormat)fmt;
+    c.input_format = (SequenceFormat)in_fmt;
+    if (have_quality) c.min_quality = (int)quality;
+    return c;
+}
+
+// kmerust query <INDEX> --sequences <PATH> [-i FMT] [-Q N] [-f summary|profile] [-q]
+struct QuerySequencesArgs {
+    std::string error, index, path;
+    bool quiet = false;
+    SequenceFormat input_format = SequenceFormat::Auto;
+    ProfileFormat format = ProfileFormat::Summary;
+    int min_quality = -1;
+    size_t batch_bytes = 0;  // --__batch-kb, a hidden test hook as __parse: KiB of flat records per kh_profile call
+};
+inline QuerySequencesArgs parse_query_sequences_args(const std::vector<std::string> &args) {
+    QuerySequencesArgs c;
+    size_t fmt = 0, in_fmt = 0;
+    uint64_t quality = 0, batch_kb = 0;
+    bool have_quality = false, have_path = false;
+    std::vector<std::string> pos;
+    const Command cmd = {{flag("-q", "--quiet", &c.quiet), text(nullptr, "--sequences", "<PATH>", &c.path, &have_path),
+                          choice("-f", "--format", "<FORMAT>", PROFILE_FORMATS, &fmt), choice("-i", "--input-format", "<INPUT_FORMAT>", INPUT_FORMATS, &in_fmt),
+                          number("-Q", "--min-quality", "<MIN_QUALITY>", &quality, 255, &have_quality), number(nullptr, "--__batch-kb", "<N>", &batch_kb, 1u << 22)},
+                         {"<INDEX>"}, 1, "Usage: kmerust query <INDEX> --sequences <PATH>"};
+    c.error = parse_args(cmd, args, &pos);
+    if (c.error.empty()) c.error = missing_args(cmd, pos);
+    if (c.error.empty() && !have_path) c.error = std::string("the following required arguments were not provided:\n  --sequences <PATH>\n\n") + cmd.usage;
+    if (!pos.empty()) c.index = pos[0];
+    c.format = (ProfileFormat)fmt;
+    c.input_format = (SequenceFormat)in_fmt;
+    if (have_quality) c.min_quality = (int)quality;
+    c.batch_bytes = (size_t)batch_kb << 10;
+    return c;
+}
+
+// kmerust filter <INDEX> <PATH> [-i FMT] [-Q N] [--min-count LO] [--max-count HI] [--min-kmers N] [--min-fraction F] [-v] [-q]
+struct FilterArgs {
+    std::string error, index, path;
+    bool quiet = false;
+    SequenceFormat input_format = SequenceFormat::Auto;
+    FilterRule rule;
+    int min_quality = -1;
+    size_t batch_bytes = 0;  // --__batch-kb, as for query --sequences
+};
+inline FilterArgs parse_filter_args(const std::vector<std::string> &args) {
+    FilterArgs c;
+    size_t in_fmt = 0;
+    uint64_t quality = 0, batch_kb = 0, lo = c.rule.min_count, hi = c.rule.max_count;
+    bool have_quality = false;
+    std::vector<std::string> pos;
+    const Command cmd = {{flag("-q", "--quiet", &c.quiet), flag("-v", "--invert", &c.rule.invert),
+                          choice("-i", "--input-format", "<INPUT_FORMAT>", INPUT_FORMATS, &in_fmt),
+                          number("-Q", "--min-quality", "<MIN_QUALITY>", &quality, 255, &have_quality),
+                          number(nullptr, "--min-count", "<LO>", &lo, 0xFFFFFFFFull), number(nullptr, "--max-count", "<HI>", &hi, 0xFFFFFFFFull),
+                          number(nullptr, "--min-kmers", "<N>", &c.rule.min_kmers), custom(nullptr, "--min-fraction", "<F>", check_fraction, &c.rule.min_fraction),
+                          number(nullptr, "--__batch-kb", "<N>", &batch_kb, 1u << 22)},
+                         {"<INDEX>", "<PATH>"}, 2, "Usage: kmerust filter <INDEX> <PATH>"};
+    c.error = parse_args(cmd, args, &pos);
+    if (c.error.empty()) c.error = missing_args(cmd, pos);
+    if (pos.size() > 0) c.index = pos[0];
+    if (pos.size() > 1) c.path = pos[1];
+    c.input_format = (SequenceFormat)in_fmt;
+    c.rule.min_count = (uint32_t)lo;
+    c.rule.max_count = (uint32_t)hi;
+    if (have_quality) c.min_quality = (int)quality;
+    c.batch_bytes = (size_t)batch_kb << 10;
+    return c;
+}
+
+// kmerust compare <INDEX_A> <INDEX_B> [--min-count-a N] [--min-count-b N] [-f tsv|json] [-q]
+// kmerust combine <OP> <INDEX_A> <INDEX_B> [-c CALC] [--min-count-a N] [--min-count-b N] [-m N] [-f FORMAT] [--save OUT] [--sorted] [-q]
+struct TwoIndexArgs {
+    std::string error, op_name, index_a, index_b, save;  // op_name ... sorted: combine only
+    bool quiet = false, json = false, sorted = false;
+    OutputFormat format = OutputFormat::Fasta;
+    uint32_t op = 0, calc = KH_CALC_SUM;  // KH_SET_*, KH_CALC_*
+    uint64_t min_a = 1, min_b = 1, min_count = 1;
+};
+inline TwoIndexArgs parse_two_index_args(const std::vector<std::string> &args, bool combine) {
+    TwoIndexArgs c;
+    size_t fmt = 0, calc = KH_CALC_SUM - 1, op = 0;
+    std::vector<std::string> pos;
+    Command cmd = {{flag("-q", "--quiet", &c.quiet), number(nullptr, "--min-count-a", "<N>", &c.min_a), number(nullptr, "--min-count-b", "<N>", &c.min_b),
+                    choice("-f", "--format", "<FORMAT>", combine ? OUTPUT_FORMATS : COMPARE_FORMATS, &fmt)},
+                   {"<INDEX_A>", "<INDEX_B>"}, 2, "Usage: kmerust compare <INDEX_A> <INDEX_B>"};
+    if (combine) {
+        cmd.opts.insert(cmd.opts.end(), {choice("-c", "--calc", "<CALC>", CALCS, &calc), number("-m", "--min-count", "<MIN_COUNT>", &c.min_count),
+                                         text(nullptr, "--save", "<SAVE>", &c.save), flag(nullptr, "--sorted", &c.sorted)});
+        cmd.positionals.insert(cmd.positionals.begin(), "<OP>");
+        cmd.required = 3;
+        cmd.usage = "Usage: kmerust combine <OP> <INDEX_A> <INDEX_B>";
+    }
+    c.error = parse_args(cmd, args, &pos);
+    if (c.error.empty() && combine && !pos.empty()) c.error = parse_choice(pos[0], "<OP>", SET_OPS, &op);  // (before a missing index is)
+    if (c.error.empty()) c.error = missing_args(cmd, pos);
+    if (!c.error.empty()) return c;
+    if (combine) c.op_name = pos[0], c.op = (uint32_t)op + 1, c.calc = (uint32_t)calc + 1, c.format = (OutputFormat)fmt;
+    else c.json = fmt == 1;
+    c.index_a = pos[cmd.required - 2];
+    c.index_b = pos[cmd.required - 1];
+    return c;
+}
+inline TwoIndexArgs parse_compare_args(const std::vector<std::string> &args) { return parse_two_index_args(args, false); }
+inline TwoIndexArgs parse_combine_args(const std::vector<std::string> &args) { return parse_two_index_args(args, true); }
+
+// kmerust graph <INDEX> [-m N] [-f summary|tsv|json] [--sorted], kmerust unitigs <INDEX> [-m N] [-f fasta|summary] and
+// kmerust gfa <INDEX> [-m N] [-f gfa|summary].  format: the position in the command's list = the value of its GraphFormat / UnitigFormat /
+// GfaFormat.
+struct IndexArgs {
+    std::string error, index;
+    uint64_t min_count = 1;
+    size_t format = 0;
+    bool sorted = false;  // graph only
+};
+inline IndexArgs parse_index_args(const std::vector<std::string> &args, const Choices &formats, bool with_sorted, const char *usage) {
+    IndexArgs c;
+    std::vector<std::string> pos;
+    Command cmd = {{choice("-f", "--format", "<FORMAT>", formats, &c.format), number("-m", "--min-count", "<MIN_COUNT>", &c.min_count)}, {"<INDEX>"}, 1, usage};
+    if (with_sorted) cmd.opts.push_back(flag(nullptr, "--sorted", &c.sorted));
+    c.error = parse_args(cmd, args, &pos);
+    if (c.error.empty()) c.error = missing_args(cmd, pos);
+    if (!pos.empty()) c.index = pos[0];
+    return c;
+}
+inline IndexArgs parse_graph_args(const std::vector<std::string> &args) { return parse_index_args(args, GRAPH_FORMATS, true, "Usage: kmerust graph <INDEX>"); }
+inline IndexArgs parse_unitigs_args(const std::vector<std::string> &args) { return parse_index_args(args, UNITIG_FORMATS, false, "Usage: kmerust unitigs <INDEX>"); }
+inline IndexArgs parse_gfa_args(const std::vector<std::string> &args) { return parse_index_args(args, GFA_FORMATS, false, "Usage: kmerust gfa <INDEX>"); }
+
+inline ClipArgs parse_clip_args(const std::vector<std::string> &args) {
+    ClipArgs c;
+    size_t fmt = 0;
+    std::vector<std::string> pos;
+    const Command cmd = {{flag("-q", "--quiet", &c.quiet), flag(nullptr, "--sorted", &c.sorted), choice("-f", "--format", "<FORMAT>", OUTPUT_FORMATS, &fmt),
+                          number("-m", "--min-count", "<MIN_COUNT>", &c.min_count), number(nullptr, "--max-kmers", "<L>", &c.max_kmers, UINT64_MAX, &c.have_max_kmers),
+                          number(nullptr, "--rounds", "<R>", &c.rounds), text(nullptr, "--save", "<SAVE>", &c.save)},
+                         {"<INDEX>"}, 1, "Usage: kmerust clip <INDEX>"};
+    c.error = parse_args(cmd, args, &pos);
+    if (c.error.empty()) c.error = missing_args(cmd, pos);
+    c.have_index = !pos.empty();
+    if (c.have_index) c.index = pos[0];
+    c.format = (OutputFormat)fmt;
+    return c;
+}
 
 }  // namespace kmerust
