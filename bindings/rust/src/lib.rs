@@ -165,6 +165,11 @@ pub mod sys {
 }
 
 /// Errors of the device path.  `KmerLength` is `KmerLengthError` of `src/error.rs:86-95`.
+/// `Device` carries the status text of the C ABI and `kh_last_error`.  Out of memory (`KH_ERR_OOM`) follows the contract of
+/// `include/kmerhip.h`, "Allocation failures": a method that only reads the table (`profile*`, `compare`, `graph_*`, `unitigs*`,
+/// the results) leaves the map usable and unchanged, so it can be called again; one that writes it (`build*`, `push_text`,
+/// `combine_into` / `clip_tips_into` on their target) leaves the map poisoned -- every later call fails with "invalid context
+/// state" until the context is reset (`kh_reset`: an empty, usable map) or dropped.
 #[derive(Debug, thiserror::Error)]
 pub enum HipError {
     #[error("k-mer length {k} is out of range: must be between 1 and 32")]

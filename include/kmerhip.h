@@ -66,6 +66,31 @@ typedef enum kh_status {
                                kh_last_error() names the rank); every rank leaves the merge together */
 } kh_status;
 
+/* Allocation failures: what KH_ERR_OOM leaves behind.  One rule per kind of call; the comments further down only add to it.
+ *   - A READING call takes the table as it is and allocates only for itself: kh_result_size / _copy / _copy_device / _sorted*,
+ *     kh_result_text_*, kh_histogram, kh_lookup, kh_profile*, kh_profile_records*, kh_compare, kh_graph_*, kh_unitigs_* and the
+ *     src side of kh_clip_tips_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
+ *     allocation, the table is unchanged and the context is NOT poisoned: the same call can be made again.  What the call
+ *     allocated is released, except the scratch the context keeps for the next such call where that had been allocated
+ *     before the failure: the pinned staging chunks and the copy stream of the host forms, the scan scratch (not after the
+ *     sorted results, kh_unitigs_begin* and kh_clip_tips_into: there nothing stays), the tile arrays of a text stream, the
+ *     chunk and row buffers of kh_profile / kh_profile_records, the words of kh_compare and kh_graph_stats.  kh_destroy
+ *     releases them.  (Pushes that were still pending when the reading call came are counted first, as a writing call.)
+ *   - A WRITING call changes the table: the pushes and the counting they trigger (also when a later call counts them), growth,
+ *     the widening of the 8-byte image, kh_merge_*, and the dst of kh_combine_into / kh_clip_tips_into.  When one of its
+ *     allocations fails it returns KH_ERR_OOM, the table's content is unspecified and the context is POISONED: every later
+ *     call except kh_reset, kh_destroy and kh_last_error returns KH_ERR_STATE.  A failure that the call can work round is
+ *     no failure: a smaller text buffer, the 16-byte table instead of its 8-byte image, the partition buffers given back for
+ *     an exchange's scratch, the exchange's own digests instead of the kernels' -- KH_OK, and the counts are exact.
+ *     (One exception, kh_merge_across: scratch of the exchange that does not fit even then is KH_ERR_OOM WITHOUT poisoning;
+ *     the table's content is unspecified until kh_reset all the same, as after any failed merge.)
+ *     The exports (kh_export_*_device, kh_region_unit_counts_device) and kh_set_shard follow this rule too: they enter the context
+ *     as a writing call does (pending pushes are counted, most of them widen the 8-byte image), and their own scratch is the
+ *     context's -- KH_ERR_OOM poisons, the table itself is intact, kh_reset starts over.
+ *   - kh_reset ends a poisoning by KH_ERR_OOM or KH_ERR_TABLE_FULL and leaves an empty, fully usable context.  A poisoning by
+ *     KH_ERR_HIP stays (KH_ERR_STATE): nothing is known about the device; kh_destroy is what is left.
+ *   - kh_create that fails returns KH_ERR_OOM with *out NULL and nothing left allocated. */
+
 typedef struct kh_ctx kh_ctx;
 
 /* Counter configuration.  Mirrors what the reference passes across its seam:

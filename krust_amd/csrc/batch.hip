@@ -145,11 +145,11 @@ int finish_batch(kh_ctx *c, const kh::PartGeom &g, PT *bufB, const u64 *bend, u6
     if (nar && c->ntab_cap != c->cap) {
         if (c->ntab) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            (void)hipFree(c->ntab);
+            (void)dev_free(c->ntab);
             c->ntab = nullptr;
             c->ntab_cap = 0;
         }
-        if (hipMalloc((void **)&c->ntab, c->cap * sizeof(u64)) != hipSuccess) {  // (no room for the image: the 16-byte table it is)
+        if (dev_malloc((void **)&c->ntab, c->cap * sizeof(u64)) != hipSuccess) {  // (no room for the image: the 16-byte table it is)
             (void)hipGetLastError();
             c->ntab = nullptr;
             nar = false;
@@ -347,42 +347,41 @@ int partition_batch(kh_ctx *c, const RangeArgs &ra, GeomChoice &gc, u64 tile0, u
     const u64 max_blocks = pool_chunks / kh::CPB + P1 + 1;
     int rc;
     // ---- what level 1 needs: the pool and its metadata (independent of the table's size) ----
-    if (!c->moff) {  // fixed-size scratch, allocated once
-        u64 z = 0;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->moff, &z, (u64)kh::MAX_P1 + 1, "hipMalloc(moff)")) != KH_OK) return rc;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->nch, &z, (u64)kh::MAX_P1 + 1, "hipMalloc(nch)")) != KH_OK) return rc;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->info, &z, 8, "hipMalloc(info)")) != KH_OK) return rc;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->pcount, &z, (u64)kh::MAX_P1, "hipMalloc(pcount)")) != KH_OK) return rc;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->pstart, &z, (u64)kh::MAX_P1 + 1, "hipMalloc(pstart)")) != KH_OK) return rc;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->pool_next, &z, 1, "hipMalloc(pool_next)")) != KH_OK) return rc;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->ptotal, &z, (u64)kh::MAX_P1, "hipMalloc(ptotal)")) != KH_OK) return rc;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->pcap, &z, (u64)kh::MAX_P1, "hipMalloc(pcap)")) != KH_OK) return rc;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->ovf, &z, 4, "hipMalloc(ovf)")) != KH_OK) return rc;
-        z = 0;
-        if ((rc = ensure_buf(c, &c->heavy, &z, (u64)kh::MAX_P1, "hipMalloc(heavy)")) != KH_OK) return rc;
+    {   // fixed-size scratch, allocated once -- each array on its OWN pointer: a context whose first batch ran out of memory half-way
+        // through this list (and was then reset) takes up where it stopped, instead of launching level 1 on the arrays it never got
+        auto fixed = [&](auto **ptr, u64 entries, const char *what) -> int {
+            u64 z = *ptr ? entries : 0;
+            return ensure_buf(c, ptr, &z, entries, what);
+        };
+        if ((rc = fixed(&c->moff, (u64)kh::MAX_P1 + 1, "hipMalloc(moff)")) != KH_OK) return rc;
+        if ((rc = fixed(&c->nch, (u64)kh::MAX_P1 + 1, "hipMalloc(nch)")) != KH_OK) return rc;
+        if ((rc = fixed(&c->info, 8, "hipMalloc(info)")) != KH_OK) return rc;
+        if ((rc = fixed(&c->pcount, (u64)kh::MAX_P1, "hipMalloc(pcount)")) != KH_OK) return rc;
+        if ((rc = fixed(&c->pstart, (u64)kh::MAX_P1 + 1, "hipMalloc(pstart)")) != KH_OK) return rc;
+        if ((rc = fixed(&c->pool_next, 1, "hipMalloc(pool_next)")) != KH_OK) return rc;
+        if ((rc = fixed(&c->ptotal, (u64)kh::MAX_P1, "hipMalloc(ptotal)")) != KH_OK) return rc;
+        if ((rc = fixed(&c->pcap, (u64)kh::MAX_P1, "hipMalloc(pcap)")) != KH_OK) return rc;
+        if ((rc = fixed(&c->ovf, 4, "hipMalloc(ovf)")) != KH_OK) return rc;
+        if ((rc = fixed(&c->heavy, (u64)kh::MAX_P1, "hipMalloc(heavy)")) != KH_OK) return rc;
     }
     if ((rc = ensure_buf(c, &c->blocks, &c->blocks_cap, max_blocks, "hipMalloc(blocks)")) != KH_OK) return rc;
+    // (a capacity kept beside its pointers is ZERO while they are re-allocated: ensure_buf frees the old array first, and a failure
+    //  must not leave the old capacity standing over a null pointer -- the next, smaller batch would skip the allocation)
     if (c->pool_cap < pool_chunks) {
-        u64 z = c->chunk_part ? c->pool_cap : 0;
+        const u64 have = c->pool_cap;
+        c->pool_cap = 0;
+        u64 z = c->chunk_part ? have : 0;
         if ((rc = ensure_buf(c, &c->chunk_part, &z, pool_chunks, "hipMalloc(chunk_part)")) != KH_OK) return rc;
-        z = c->fill8 ? c->pool_cap : 0;
+        z = c->fill8 ? have : 0;
         if ((rc = ensure_buf(c, &c->fill8, &z, pool_chunks, "hipMalloc(fill8)")) != KH_OK) return rc;
-        z = c->plist ? c->pool_cap : 0;
+        z = c->plist ? have : 0;
         if ((rc = ensure_buf(c, &c->plist, &z, pool_chunks, "hipMalloc(plist)")) != KH_OK) return rc;
         c->pool_cap = pool_chunks;
     }
     const u64 a_bytes = pool_chunks * kh::CHUNK_PAY * sizeof(PT);  // A: the level-1 pool
     if (c->key_cap < a_bytes) {  // (capacities in BYTES)
         u64 z = c->keysA ? c->key_cap : 0;
+        c->key_cap = 0;
         if ((rc = ensure_buf(c, &c->keysA, &z, a_bytes, "hipMalloc(keysA)")) != KH_OK) return rc;
         c->key_cap = a_bytes;
     }
@@ -570,9 +569,11 @@ int partition_batch(kh_ctx *c, const RangeArgs &ra, GeomChoice &gc, u64 tile0, u
     const u64 nregions = kh::part_regions(g);
     const u64 n2 = max_blocks * g.b2;
     if (c->h2_cap < n2) {  // H2 and O2 grow together
-        u64 z = c->h2_cap;
+        const u64 have = c->h2_cap;
+        c->h2_cap = 0;  // (zero while they are re-allocated: see pool_cap)
+        u64 z = c->H2 ? have : 0;
         if ((rc = ensure_buf(c, &c->H2, &z, n2, "hipMalloc(H2)")) != KH_OK) return rc;
-        z = c->O2 ? c->h2_cap + 1 : 0;
+        z = c->O2 ? have + 1 : 0;
         if ((rc = ensure_buf(c, &c->O2, &z, n2 + 1, "hipMalloc(O2)")) != KH_OK) return rc;
         c->h2_cap = n2;
     }
@@ -621,6 +622,7 @@ int partition_batch(kh_ctx *c, const RangeArgs &ra, GeomChoice &gc, u64 tile0, u
         // (8-byte payloads end in the 16-byte table: its room too, where it does not exist yet)
         if (sized_narrow && ((u64)fr + c->keyb_cap < b_bytes_wide + (c->table ? 0 : c->cap * sizeof(Slot)) + (4ull << 30) || c->knobs.l2_no_room_wide)) return KH_RETRY_WIDE;
         u64 z = c->keysB ? c->keyb_cap : 0;
+        c->keyb_cap = 0;
         const int r = ensure_buf(c, &c->keysB, &z, b_bytes_wide, "hipMalloc(keysB)");
         if (r == KH_OK) c->keyb_cap = b_bytes_wide;
         return r;
@@ -629,12 +631,14 @@ int partition_batch(kh_ctx *c, const RangeArgs &ra, GeomChoice &gc, u64 tile0, u
         if ((rc = room_for_wide()) != KH_OK) return rc;
     } else if (c->keyb_cap < b_bytes) {
         u64 z = c->keysB ? c->keyb_cap : 0;
+        c->keyb_cap = 0;
         if ((rc = ensure_buf(c, &c->keysB, &z, b_bytes, "hipMalloc(keysB)")) != KH_OK) return rc;
         c->keyb_cap = b_bytes;
     }
     PT *bufA = reinterpret_cast<PT *>(c->keysA), *bufB = reinterpret_cast<PT *>(c->keysB);  // (bufB: again after a re-allocation)
     if (arena && c->ovf_cap < ovf_need) {
         u64 z = c->ovf_list ? c->ovf_cap : 0;
+        c->ovf_cap = 0;
         if ((rc = ensure_buf(c, &c->ovf_list, &z, ovf_need, "hipMalloc(ovf_list)")) != KH_OK) return rc;
         c->ovf_cap = ovf_need;
     }

@@ -29,12 +29,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <mutex>
 #include <new>
 #include <string>
 #include <thread>
 #include <type_traits>
 #include <vector>
 
+#include "alloc_inject.h"
 #include "kernels.hip.h"
 #include "partition.hip.h"
 
@@ -116,6 +118,8 @@ struct Knobs {
     u64 table_room_mb = 0;           // KMERHIP_TABLE_ROOM_MB: what the sample-sized table may take, as if the device had no more
     bool stop_after_p1 = false, stop_after_p2 = false;  // ablation builds (KH_ABL*)
     u64 profile_chunk_kb = 0;        // KMERHIP_PROFILE_CHUNK_KB: window starts per chunk of kh_profile, in units of 1024 (0: sized from the call)
+    // KMERHIP_ALLOC_FAIL=n | n+, KMERHIP_ALLOC_TRACE=path: the n-th allocation through dev_malloc / pin_malloc (below) fails; every
+    // allocation, release and injected failure is appended to a file.  Not fields: read at every allocation, one count per process.
     // KMERHIP_GRID_CAP: the most workgroups of a capped-grid launch (0 / unset: GRID_CAP).  Not a field: one value per process,
     // g_grid_cap below, which read_knobs sets -- and the context of the product library stays the size it was.
 };
@@ -134,6 +138,42 @@ extern std::atomic<int> g_grid_cap;  // (contexts on several threads re-read the
 inline int grid_cap() { return g_grid_cap.load(std::memory_order_relaxed); }
 #else
 constexpr int grid_cap() { return GRID_CAP; }
+#endif
+
+// Every device and pinned-host allocation and release of the library goes through these four.  The product library: forwards
+// to the runtime and nothing else.  The test build: KMERHIP_ALLOC_FAIL=n makes the n-th allocation through them fail (n+: that
+// one and every later one) -- hipErrorOutOfMemory without a call of the runtime, the pointer null; one 1-based count per
+// process for both kinds, restarted whenever the variable's value changes (alloc_inject.h) -- and KMERHIP_ALLOC_TRACE=path
+// appends one line per event to that file:  "A dev|pin <pointer> <bytes>"  an allocation that succeeded,  "F <pointer>"  a
+// release,  "X <ordinal> dev|pin <bytes>"  an injected failure.  Both are read at every call (tests/test_gpu_alloc_fail.py).
+#if KH_TESTING
+bool alloc_inject_fails(const char *kind, size_t bytes);                  // kmerhip.hip
+void alloc_trace_event(char ev, const char *kind, const void *p, size_t bytes);
+inline hipError_t dev_malloc(void **p, size_t bytes) {
+    if (alloc_inject_fails("dev", bytes)) { *p = nullptr; return hipErrorOutOfMemory; }
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) alloc_trace_event('A', "dev", *p, bytes);
+    return e;
+}
+inline hipError_t pin_malloc(void **p, size_t bytes, unsigned flags) {
+    if (alloc_inject_fails("pin", bytes)) { *p = nullptr; return hipErrorOutOfMemory; }
+    const hipError_t e = hipHostMalloc(p, bytes, flags);
+    if (e == hipSuccess) alloc_trace_event('A', "pin", *p, bytes);
+    return e;
+}
+inline hipError_t dev_free(void *p) {
+    if (p) alloc_trace_event('F', nullptr, p, 0);
+    return hipFree(p);
+}
+inline hipError_t pin_free(void *p) {
+    if (p) alloc_trace_event('F', nullptr, p, 0);
+    return hipHostFree(p);
+}
+#else
+inline hipError_t dev_malloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+inline hipError_t pin_malloc(void **p, size_t bytes, unsigned flags) { return hipHostMalloc(p, bytes, flags); }
+inline hipError_t dev_free(void *p) { return hipFree(p); }
+inline hipError_t pin_free(void *p) { return hipHostFree(p); }
 #endif
 
 }  // namespace khi
@@ -362,6 +402,7 @@ struct kh_ctx {
     } un;
 
     bool poisoned = false;
+    int poisoned_by = KH_OK;  // the status that poisoned it: kh_reset lifts KH_ERR_OOM and KH_ERR_TABLE_FULL, never KH_ERR_HIP
     std::string last_error;
 };
 
@@ -374,9 +415,22 @@ inline int fail(kh_ctx *c, int code, const char *what, hipError_t e = hipSuccess
             c->last_error += ": ";
             c->last_error += hipGetErrorString(e);
         }
-        if (code == KH_ERR_HIP || code == KH_ERR_TABLE_FULL || code == KH_ERR_OOM) c->poisoned = true;
+        if (code == KH_ERR_HIP || code == KH_ERR_TABLE_FULL || code == KH_ERR_OOM) {
+            if (!c->poisoned || code == KH_ERR_HIP) c->poisoned_by = code;  // (kh_reset lifts what no runtime error caused)
+            c->poisoned = true;
+        }
     }
     return code;
+}
+// KH_ERR_OOM of a READING call (include/kmerhip.h, "Allocation failures"): an allocation of this call alone failed, the table
+// is untouched -- the error text names the allocation, and the context is not poisoned.
+inline int soft_oom(kh_ctx *c, const char *what, hipError_t e = hipSuccess) {
+    c->last_error = what;
+    if (e != hipSuccess) {
+        c->last_error += ": ";
+        c->last_error += hipGetErrorString(e);
+    }
+    return KH_ERR_OOM;
 }
 
 #define HIP_TRY(c, call)                                              \
@@ -417,7 +471,10 @@ void *borrow(kh_ctx *c, u64 bytes);   // `bytes` of the idle partition buffers (
 u64 borrow_room(const kh_ctx *c);     // the largest single request borrow() could serve now
 int end_borrow(kh_ctx *c);            // the partition buffers are about to be written (or freed): a borrowed table moves to memory of its own
 void drop_table(kh_ctx *c);           // the 16-byte table is no longer needed: freed, unless it was borrowed
-int device_scan(kh_ctx *c, const uint32_t *in, u64 n, u64 *out);
+// soft: the context's scan scratch fails as a reading call's (ensure_buf).  scratch: device_scan_scratch(n) bytes of the caller's own to
+// use instead -- the calls that promise to leave nothing allocated (sort.hip, unitig.hip) take them from their SortScratch.
+int device_scan(kh_ctx *c, const uint32_t *in, u64 n, u64 *out, bool soft = false, u64 *scratch = nullptr);
+inline u64 device_scan_scratch(u64 n) { return ((n + kh::SCAN_CHUNK - 1) / kh::SCAN_CHUNK + 2) * sizeof(u64); }
 int zero_cursors(kh_ctx *c);
 // the live pairs with count >= min_count into device arrays of capacity cap, in no particular order (what kh_result_copy_device
 // does once it has entered the context): *n = pairs written; KH_ERR_RANGE when the table holds more than cap
@@ -496,8 +553,9 @@ struct StageTimer {
 
 // ---- device scratch management for the partitioned path --------------------------------------
 inline double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// soft: the non-poisoning form, for the scratch a reading call keeps in the context -- KH_ERR_OOM through soft_oom()
 template <typename T>
-int ensure_buf(kh_ctx *c, T **ptr, u64 *cap, u64 need, const char *what) {
+int ensure_buf(kh_ctx *c, T **ptr, u64 *cap, u64 need, const char *what, bool soft = false) {
     if (*cap >= need && *ptr) return KH_OK;
     const double t0 = c->trace ? wall_ms() : 0.0;
     struct Tr {
@@ -506,14 +564,15 @@ int ensure_buf(kh_ctx *c, T **ptr, u64 *cap, u64 need, const char *what) {
     } tr{c, t0, what, need * sizeof(T)};
     if (*ptr) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(*ptr);
+        (void)dev_free(*ptr);
         *ptr = nullptr;
         *cap = 0;
     }
-    hipError_t e = hipMalloc((void **)ptr, need * sizeof(T));
+    hipError_t e = dev_malloc((void **)ptr, need * sizeof(T));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return fail(c, KH_ERR_OOM, what, e);
+        *ptr = nullptr;
+        return soft ? soft_oom(c, what, e) : fail(c, KH_ERR_OOM, what, e);
     }
     *cap = need;
     return KH_OK;

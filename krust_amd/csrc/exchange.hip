@@ -116,7 +116,7 @@ struct LocalHub {
             std::lock_guard<std::mutex> lk(m);
             k.swap(kept);
         }
-        for (void *p : k) (void)hipFree(p);
+        for (void *p : k) (void)dev_free(p);
     }
     ~LocalHub() { release_kept(); }
 };
@@ -354,7 +354,7 @@ struct DevBuf {  // scratch of one merge; freed when it goes out of scope
         if (!p) return;
         if (owned) {
             if (tl_hub && tl_hub->is_poisoned()) tl_hub->keep(p);  // (a peer may still be reading it: LocalHub::keep)
-            else (void)hipFree(p);
+            else (void)dev_free(p);
         }
         p = nullptr;
         owned = true;
@@ -366,12 +366,12 @@ struct DevBuf {  // scratch of one merge; freed when it goes out of scope
             owned = false;
             return KH_OK;
         }
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+        hipError_t e = dev_malloc(&p, bytes ? bytes : 16);
         // the partition buffers of the counting that is over: room for this -- unless parts of them are lent out to this very merge
         if (e != hipSuccess && (c->keysA || c->keysB) && !(c->borrow_off[0] | c->borrow_off[1])) {
             (void)hipGetLastError();
             p = nullptr;
-            if (release_part_buffers(c) == KH_OK) e = hipMalloc(&p, bytes ? bytes : 16);
+            if (release_part_buffers(c) == KH_OK) e = dev_malloc(&p, bytes ? bytes : 16);
         }
         if (e != hipSuccess) {
             (void)hipGetLastError();
@@ -1214,8 +1214,8 @@ void comm_release(kh_ctx *c) {
     if (cm->xs && !cm->dead.load()) (void)hipStreamSynchronize(cm->xs);
     if (cm->nccl && !cm->dead.load()) (void)ncclCommDestroy(cm->nccl);  // (an aborted communicator is gone already)
     if (cm->hub && cm->rank < cm->hub->xs.size()) cm->hub->xs[cm->rank] = nullptr;
-    if (cm->d_small) (void)hipFree(cm->d_small);
-    if (cm->h_small) (void)hipHostFree(cm->h_small);
+    if (cm->d_small) (void)dev_free(cm->d_small);
+    if (cm->h_small) (void)pin_free(cm->h_small);
     if (cm->xs) (void)hipStreamDestroy(cm->xs);
     delete cm;
     c->comm = nullptr;
@@ -1243,7 +1243,7 @@ int comm_setup(kh_ctx *c, uint32_t nranks, uint32_t rank, const ncclUniqueId *id
     if (hub) cm->seen = hub->n;
     if (rc == KH_OK && !hub) {
         const size_t n = (size_t)(1 + nranks) * SMALL_MAX * sizeof(u64);
-        if (hipMalloc((void **)&cm->d_small, n) != hipSuccess || hipHostMalloc((void **)&cm->h_small, n, hipHostMallocDefault) != hipSuccess) {
+        if (dev_malloc((void **)&cm->d_small, n) != hipSuccess || pin_malloc((void **)&cm->h_small, n, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
             rc = fail(c, KH_ERR_OOM, "exchange staging");
         }

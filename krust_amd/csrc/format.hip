@@ -21,12 +21,12 @@ void text_release(kh_ctx *c) {
     for (int i = 0; i < 2; ++i) {
         if (c->ts.ch[i].done) (void)hipEventDestroy(c->ts.ch[i].done);
         c->ts.ch[i].done = nullptr;
-        if (c->ts_own[i]) (void)hipFree(c->ts_own[i]);
+        if (c->ts_own[i]) (void)dev_free(c->ts_own[i]);
         c->ts_own[i] = nullptr;
     }
     void *bufs[] = {c->ts_trec, c->ts_tbyt, c->ts_roff, c->ts_boff, c->ts_skey, c->ts_scnt};
     for (void *p : bufs)
-        if (p) (void)hipFree(p);
+        if (p) (void)dev_free(p);
     c->ts_trec = c->ts_tbyt = nullptr;
     c->ts_roff = c->ts_boff = nullptr;
     c->ts_skey = c->ts_scnt = nullptr;
@@ -58,7 +58,7 @@ int chunk_memory(kh_ctx *c, int i) {
     u64 want = TS_CHUNK_MIN;
     while (want < TS_CHUNK_MAX && want < c->ts.rec_bytes) want *= 4;
     want = std::min(want, TS_CHUNK_MAX);
-    int rc = ensure_buf(c, &c->ts_own[i], &c->ts_own_cap[i], want, "hipMalloc(text chunk)");
+    int rc = ensure_buf(c, &c->ts_own[i], &c->ts_own_cap[i], want, "hipMalloc(text chunk)", true);
     if (rc != KH_OK) return rc;
     ch.d = c->ts_own[i];
     ch.cap = c->ts_own_cap[i];
@@ -209,28 +209,28 @@ extern "C" int kh_result_text_begin(kh_ctx *c, uint32_t format, uint64_t min_cou
     uint64_t sorted_n = 0;
     if (sorted) {  // the stream's own copy of the result, ascending by key; the sort's scratch goes back before any chunk is placed
         if ((rc = kh_result_size(c, min_count, &sorted_n)) != KH_OK) return rc;
-        if ((rc = ensure_buf(c, &c->ts_skey, &c->ts_skey_cap, std::max<u64>(sorted_n, 1), "hipMalloc(sorted text pairs)")) != KH_OK) return rc;
-        if ((rc = ensure_buf(c, &c->ts_scnt, &c->ts_scnt_cap, std::max<u64>(sorted_n, 1), "hipMalloc(sorted text pairs)")) != KH_OK) return rc;
+        if ((rc = ensure_buf(c, &c->ts_skey, &c->ts_skey_cap, std::max<u64>(sorted_n, 1), "hipMalloc(sorted text pairs)", true)) != KH_OK) return rc;
+        if ((rc = ensure_buf(c, &c->ts_scnt, &c->ts_scnt_cap, std::max<u64>(sorted_n, 1), "hipMalloc(sorted text pairs)", true)) != KH_OK) return rc;
         SortScratch sc(c);
         if ((rc = sorted_into(c, c->ts_skey, c->ts_scnt, sorted_n, min_count, sc)) != KH_OK) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     const u64 ntiles = std::max<u64>(((sorted ? sorted_n : c->cap) + kh::FMT_TILE - 1) / kh::FMT_TILE, 1);
-    if ((rc = ensure_buf(c, &c->ts_trec, &c->ts_trec_cap, ntiles, "hipMalloc(text tiles)")) != KH_OK) return rc;
-    if ((rc = ensure_buf(c, &c->ts_tbyt, &c->ts_tbyt_cap, ntiles, "hipMalloc(text tiles)")) != KH_OK) return rc;
-    if ((rc = ensure_buf(c, &c->ts_roff, &c->ts_roff_cap, ntiles + 1, "hipMalloc(text tiles)")) != KH_OK) return rc;
-    if ((rc = ensure_buf(c, &c->ts_boff, &c->ts_boff_cap, ntiles + 1, "hipMalloc(text tiles)")) != KH_OK) return rc;
+    if ((rc = ensure_buf(c, &c->ts_trec, &c->ts_trec_cap, ntiles, "hipMalloc(text tiles)", true)) != KH_OK) return rc;
+    if ((rc = ensure_buf(c, &c->ts_tbyt, &c->ts_tbyt_cap, ntiles, "hipMalloc(text tiles)", true)) != KH_OK) return rc;
+    if ((rc = ensure_buf(c, &c->ts_roff, &c->ts_roff_cap, ntiles + 1, "hipMalloc(text tiles)", true)) != KH_OK) return rc;
+    if ((rc = ensure_buf(c, &c->ts_boff, &c->ts_boff_cap, ntiles + 1, "hipMalloc(text tiles)", true)) != KH_OK) return rc;
     with_loader(c, sorted, sorted_n, [&](auto ld, u64 slots) {
         hipLaunchKernelGGL(kh::fmt_size_kernel<decltype(ld)>, dim3(grid_for(ntiles * kh::BLOCK)), dim3(kh::BLOCK), 0, c->stream, ld, slots,
                            c->k, format, (u64)min_count, ntiles, c->ts_trec, c->ts_tbyt);
     });
     HIP_TRY(c, hipGetLastError());
-    if ((rc = device_scan(c, c->ts_trec, ntiles, c->ts_roff)) != KH_OK) return rc;
-    if ((rc = device_scan(c, c->ts_tbyt, ntiles, c->ts_boff)) != KH_OK) return rc;
+    if ((rc = device_scan(c, c->ts_trec, ntiles, c->ts_roff, true)) != KH_OK) return rc;
+    if ((rc = device_scan(c, c->ts_tbyt, ntiles, c->ts_boff, true)) != KH_OK) return rc;
     try {
         ts.toff.resize(ntiles + 1);
     } catch (...) {
-        return fail(c, KH_ERR_OOM, "host memory for the tile offsets");
+        return soft_oom(c, "host memory for the tile offsets");  // (a reading call: the context stays usable)
     }
     u64 nrec = 0;
     HIP_TRY(c, hipMemcpyAsync(ts.toff.data(), c->ts_boff, (ntiles + 1) * sizeof(u64), hipMemcpyDeviceToHost, c->stream));

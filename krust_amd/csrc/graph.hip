@@ -143,11 +143,6 @@ __global__ __launch_bounds__(BLOCK) void graph_kernel(SRC src, u64 s0, u64 s1, u
 namespace khi {
 namespace {
 
-int soft_oom(kh_ctx *c, const char *what) {  // (not fail(): an allocation of this call alone failed, the table is untouched)
-    c->last_error = what;
-    return KH_ERR_OOM;
-}
-
 // What all three calls do before they look at the table: neighbours of a shard's keys live on other owners.
 int graph_enter(kh_ctx *c, const char *who) {
     if (c->shard_shift) return fail(c, KH_ERR_STATE, (std::string(who) + ": the table is a shard; its k-mers' neighbours live on other owners").c_str());
@@ -191,7 +186,7 @@ extern "C" int kh_graph_stats(kh_ctx *c, uint64_t min_count, uint64_t *out) {
     int rc = graph_enter(c, "kh_graph_stats");
     if (rc != KH_OK) return rc;
     if (!c->gr_words) {
-        hipError_t e = hipMalloc((void **)&c->gr_words, KH_GRAPH_WORDS * sizeof(u64));
+        hipError_t e = dev_malloc((void **)&c->gr_words, KH_GRAPH_WORDS * sizeof(u64));
         if (e != hipSuccess) {
             (void)hipGetLastError();
             c->gr_words = nullptr;
@@ -232,9 +227,9 @@ extern "C" int kh_graph_masks(kh_ctx *c, const uint64_t *keys, uint64_t n, uint6
     // as kh_lookup: device scratch for this call alone, one launch, copy back
     u64 *dk = nullptr;
     uint8_t *dm = nullptr;
-    if (n > (~0ull >> 4) || hipMalloc((void **)&dk, n * sizeof(u64)) != hipSuccess || hipMalloc((void **)&dm, n) != hipSuccess) {
+    if (n > (~0ull >> 4) || dev_malloc((void **)&dk, n * sizeof(u64)) != hipSuccess || dev_malloc((void **)&dm, n) != hipSuccess) {
         (void)hipGetLastError();
-        if (dk) (void)hipFree(dk);
+        if (dk) (void)dev_free(dk);
         return soft_oom(c, "hipMalloc(graph masks)");
     }
     hipError_t e = hipMemcpyAsync(dk, keys, n * sizeof(u64), hipMemcpyHostToDevice, c->stream);
@@ -244,8 +239,8 @@ extern "C" int kh_graph_masks(kh_ctx *c, const uint64_t *keys, uint64_t n, uint6
     }
     const hipError_t es = hipStreamSynchronize(c->stream);  // (before the scratch is freed, whatever happened)
     if (e == hipSuccess) e = es;
-    (void)hipFree(dk);
-    (void)hipFree(dm);
+    (void)dev_free(dk);
+    (void)dev_free(dm);
     if (rc != KH_OK) return rc;
     if (e != hipSuccess) return fail(c, KH_ERR_HIP, "kh_graph_masks", e);
     return KH_OK;

@@ -55,7 +55,7 @@ void staged_memcpy(void *dst, const void *src, size_t n) {
 // travels -- each 2 x stage_bytes (bases and qualities; or one text chunk), stage_bytes = the smallest of 1 / 8 / 64 MiB that
 // holds `need` (round 5: every context that saw a host push pinned 256 MiB for them, ~50 ms -- of a ten-byte test input, and
 // of every command-line run, whose chunks are pinned and never touch the staging at all: need = 0).
-int ensure_stage(kh_ctx *c, u64 need) {
+int ensure_stage(kh_ctx *c, u64 need, bool soft = false) {  // soft: for a reading call (d2h_staged) -- KH_ERR_OOM without poisoning
     if (!c->cstream) HIP_TRY(c, hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
         if (!c->stage_done[i]) HIP_TRY(c, hipEventCreateWithFlags(&c->stage_done[i], hipEventDisableTiming));
@@ -68,14 +68,19 @@ int ensure_stage(kh_ctx *c, u64 need) {
     if (c->stage_bytes >= want) return KH_OK;
     HIP_TRY(c, hipStreamSynchronize(c->cstream));  // (nothing in flight out of the buffers about to go)
     for (int i = 0; i < 2; ++i) {
-        if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
+        if (c->h_stage[i]) (void)pin_free(c->h_stage[i]);
         c->h_stage[i] = nullptr;
         c->stage_used[i] = false;
     }
     c->stage_bytes = 0;
     for (int i = 0; i < 2; ++i) {
-        hipError_t e = hipHostMalloc((void **)&c->h_stage[i], 2 * want, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(c, KH_ERR_OOM, "hipHostMalloc(stage)", e);
+        hipError_t e = pin_malloc((void **)&c->h_stage[i], 2 * want, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (i) (void)pin_free(c->h_stage[0]);  // (nothing is in flight: the copy stream was drained above)
+            c->h_stage[0] = c->h_stage[1] = nullptr;
+            return soft ? soft_oom(c, "hipHostMalloc(stage)", e) : fail(c, KH_ERR_OOM, "hipHostMalloc(stage)", e);
+        }
     }
     c->stage_bytes = want;
     return KH_OK;
@@ -86,7 +91,7 @@ int ensure_stage(kh_ctx *c, u64 need) {
 // array cost more than the copy itself).
 int d2h_staged(kh_ctx *c, void *dst, const void *d_src, u64 bytes, hipEvent_t ready) {
     const bool pinned_dst = is_pinned_host(dst);
-    int rc = ensure_stage(c, pinned_dst ? 0 : (bytes + 1) / 2);
+    int rc = ensure_stage(c, pinned_dst ? 0 : (bytes + 1) / 2, true);  // (only reading calls copy results out)
     if (rc != KH_OK) return rc;
     if (pinned_dst) {  // a registered destination takes the DMA itself: no bounce, no first-touch faults
         if (ready) HIP_TRY(c, hipStreamWaitEvent(c->cstream, ready, 0));  // (the compute stream goes on: it formats the next chunk)
@@ -165,10 +170,10 @@ int alloc_acc(kh_ctx *c, u64 cap, bool with_qual) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->acc_has_qual = with_qual;
     for (int i = 0; i < 2; ++i) {
-        if (c->acc[i]) (void)hipFree(c->acc[i]);
+        if (c->acc[i]) (void)dev_free(c->acc[i]);
         c->acc[i] = nullptr;
         c->acc_busy[i] = false;
-        hipError_t e = hipMalloc((void **)&c->acc[i], (with_qual ? 2 : 1) * acc_stride(cap));
+        hipError_t e = dev_malloc((void **)&c->acc[i], (with_qual ? 2 : 1) * acc_stride(cap));
         if (e != hipSuccess) {
             (void)hipGetLastError();
             c->acc_cap = 0;
@@ -355,10 +360,10 @@ int text_device_scan(kh_ctx *c, hipStream_t s, const uint32_t *in, u64 n, u64 *o
     const u64 nb = (n + kh::SCAN_CHUNK - 1) / kh::SCAN_CHUNK;
     if (c->txt_scan_cap < nb + 2) {
         HIP_TRY(c, hipStreamSynchronize(s));
-        if (c->txt_scan_partial) (void)hipFree(c->txt_scan_partial);
+        if (c->txt_scan_partial) (void)dev_free(c->txt_scan_partial);
         c->txt_scan_partial = nullptr;
         c->txt_scan_cap = 0;
-        if (hipMalloc((void **)&c->txt_scan_partial, (nb + 2) * 2 * sizeof(u64)) != hipSuccess) {
+        if (dev_malloc((void **)&c->txt_scan_partial, (nb + 2) * 2 * sizeof(u64)) != hipSuccess) {
             (void)hipGetLastError();
             return fail(c, KH_ERR_OOM, "hipMalloc(text scan)");
         }
@@ -380,7 +385,7 @@ int scan_text(kh_ctx *c, const uint8_t *d_text, u64 n, int format, hipStream_t s
     const u64 need = (n + 15) / 16 * 16 + 64;  // (FASTQ: as many bytes as the text; FASTA: at most)
     int rc;
     if (!c->h_txt) {
-        hipError_t e = hipHostMalloc((void **)&c->h_txt, sizeof(*c->h_txt), hipHostMallocDefault);
+        hipError_t e = pin_malloc((void **)&c->h_txt, sizeof(*c->h_txt), hipHostMallocDefault);
         if (e != hipSuccess) return fail(c, KH_ERR_OOM, "hipHostMalloc(text scan)", e);
     }
     // room in the current buffer -- else what it holds is counted and the other buffer takes over
@@ -420,14 +425,14 @@ int scan_text(kh_ctx *c, const uint8_t *d_text, u64 n, int format, hipStream_t s
             HIP_TRY(c, hipStreamSynchronize(s));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             const double tb = wall_ms();
-            if (c->txt_acc[cur]) (void)hipFree(c->txt_acc[cur]);
+            if (c->txt_acc[cur]) (void)dev_free(c->txt_acc[cur]);
             c->txt_acc[cur] = nullptr;
             c->txt_acc_cap[cur] = 0;
-            hipError_t e = hipMalloc((void **)&c->txt_acc[cur], want);
+            hipError_t e = dev_malloc((void **)&c->txt_acc[cur], want);
             if (e != hipSuccess && want > need) {  // (no room for the generous size: what this text needs, then)
                 (void)hipGetLastError();
                 want = need;
-                e = hipMalloc((void **)&c->txt_acc[cur], want);
+                e = dev_malloc((void **)&c->txt_acc[cur], want);
             }
             if (e != hipSuccess) {
                 (void)hipGetLastError();
@@ -439,10 +444,10 @@ int scan_text(kh_ctx *c, const uint8_t *d_text, u64 n, int format, hipStream_t s
         if (with_qual && c->txt_accq_cap[cur] < c->txt_acc_cap[cur]) {
             HIP_TRY(c, hipStreamSynchronize(s));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (c->txt_accq[cur]) (void)hipFree(c->txt_accq[cur]);
+            if (c->txt_accq[cur]) (void)dev_free(c->txt_accq[cur]);
             c->txt_accq[cur] = nullptr;
             c->txt_accq_cap[cur] = 0;
-            hipError_t e = hipMalloc((void **)&c->txt_accq[cur], c->txt_acc_cap[cur]);
+            hipError_t e = dev_malloc((void **)&c->txt_accq[cur], c->txt_acc_cap[cur]);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 return fail(c, KH_ERR_OOM, "hipMalloc(text qualities)", e);
@@ -456,10 +461,10 @@ int scan_text(kh_ctx *c, const uint8_t *d_text, u64 n, int format, hipStream_t s
     auto tbuf = [&](auto **ptr, u64 *cap, u64 want, const char *what) -> int {
         if (*cap >= want && *ptr) return KH_OK;
         HIP_TRY(c, hipStreamSynchronize(s));
-        if (*ptr) (void)hipFree(*ptr);
+        if (*ptr) (void)dev_free(*ptr);
         *ptr = nullptr;
         *cap = 0;
-        if (hipMalloc((void **)ptr, want * sizeof(**ptr)) != hipSuccess) {
+        if (dev_malloc((void **)ptr, want * sizeof(**ptr)) != hipSuccess) {
             (void)hipGetLastError();
             return fail(c, KH_ERR_OOM, what);
         }
@@ -624,10 +629,10 @@ extern "C" int kh_push_text(kh_ctx *c, const uint8_t *text, uint64_t n, int form
         while (want < n + 64) want *= 2;
         HIP_TRY(c, hipStreamSynchronize(c->cstream));  // (the last text's scan read the old buffer)
         if (c->sstream) HIP_TRY(c, hipStreamSynchronize(c->sstream));
-        if (c->txt_raw2[r]) (void)hipFree(c->txt_raw2[r]);
+        if (c->txt_raw2[r]) (void)dev_free(c->txt_raw2[r]);
         c->txt_raw2[r] = nullptr;
         c->txt_raw2_cap[r] = 0;
-        if (hipMalloc((void **)&c->txt_raw2[r], want) != hipSuccess) {
+        if (dev_malloc((void **)&c->txt_raw2[r], want) != hipSuccess) {
             (void)hipGetLastError();
             return fail(c, KH_ERR_OOM, "hipMalloc(text)");
         }

@@ -167,13 +167,13 @@ namespace {
 
 constexpr u64 JOIN_WORDS = KH_CMP_WORDS + 1;  // the words of kh_compare, then the pair count of kh_combine_into
 
-int join_words(kh_ctx *c) {
+int join_words(kh_ctx *c, bool soft) {  // soft: for kh_compare, a reading call
     if (c->jn_words) return KH_OK;
-    hipError_t e = hipMalloc((void **)&c->jn_words, JOIN_WORDS * sizeof(u64));
+    hipError_t e = dev_malloc((void **)&c->jn_words, JOIN_WORDS * sizeof(u64));
     if (e != hipSuccess) {
         (void)hipGetLastError();
         c->jn_words = nullptr;
-        return fail(c, KH_ERR_OOM, "hipMalloc(join words)", e);
+        return soft ? soft_oom(c, "hipMalloc(join words)", e) : fail(c, KH_ERR_OOM, "hipMalloc(join words)", e);
     }
     return KH_OK;
 }
@@ -242,7 +242,7 @@ extern "C" int kh_compare(kh_ctx *a, kh_ctx *b, uint64_t min_a, uint64_t min_b, 
     if (rc != KH_OK) return rc;
     if ((rc = join_enter_source(a, a)) != KH_OK) return rc;
     if (b != a && (rc = join_enter_source(a, b)) != KH_OK) return rc;  // (b's stream is drained: the kernels run on a's)
-    if ((rc = join_words(a)) != KH_OK) return rc;
+    if ((rc = join_words(a, true)) != KH_OK) return rc;
     const u64 ma = min_a ? min_a : 1, mb = min_b ? min_b : 1;
     HIP_TRY(a, hipMemsetAsync(a->jn_words, 0, JOIN_WORDS * sizeof(u64), a->stream));
     if ((rc = join_launch(a, a, 0, a->cap, ma, b, mb, kh::JkStats<false>{a->jn_words})) != KH_OK) return rc;
@@ -267,7 +267,7 @@ extern "C" int kh_combine_into(kh_ctx *dst, kh_ctx *a, kh_ctx *b, uint32_t op, u
     if ((rc = join_enter_source(dst, a)) != KH_OK) return rc;
     if (b != a && (rc = join_enter_source(dst, b)) != KH_OK) return rc;  // (both source streams are drained: the kernels run on dst's)
     if ((rc = enter(dst)) != KH_OK) return rc;
-    if ((rc = join_words(dst)) != KH_OK) return rc;
+    if ((rc = join_words(dst, false)) != KH_OK) return rc;
     const u64 ma = min_a ? min_a : 1, mb = min_b ? min_b : 1;
     const u64 da = a->h_ctr->distinct, db = b->h_ctr->distinct;  // (exact: join_enter_source read them back)
     HIP_TRY(dst, hipMemsetAsync(dst->jn_words + KH_CMP_WORDS, 0, sizeof(u64), dst->stream));

@@ -9,6 +9,31 @@ namespace khi {
 
 #if KH_TESTING
 std::atomic<int> g_grid_cap{GRID_CAP};
+
+// KMERHIP_ALLOC_FAIL / KMERHIP_ALLOC_TRACE (ctx.hip.h, the four allocation wrappers): one count and one lock per process
+static std::mutex g_alloc_mu;
+static AllocInject g_alloc_inject;
+void alloc_trace_event(char ev, const char *kind, const void *p, size_t bytes) {
+    const char *path = env_of("KMERHIP_ALLOC_TRACE");
+    if (!path) return;
+    std::lock_guard<std::mutex> lk(g_alloc_mu);
+    FILE *f = fopen(path, "a");
+    if (!f) return;
+    if (ev == 'A') fprintf(f, "A %s %p %zu\n", kind, p, bytes);
+    else fprintf(f, "F %p\n", p);
+    fclose(f);
+}
+bool alloc_inject_fails(const char *kind, size_t bytes) {
+    std::lock_guard<std::mutex> lk(g_alloc_mu);
+    const uint64_t ord = g_alloc_inject.step(env_of("KMERHIP_ALLOC_FAIL"));
+    if (!ord) return false;
+    if (const char *path = env_of("KMERHIP_ALLOC_TRACE"))
+        if (FILE *f = fopen(path, "a")) {
+            fprintf(f, "X %llu %s %zu\n", (unsigned long long)ord, kind, bytes);
+            fclose(f);
+        }
+    return true;
+}
 #endif
 
 void read_knobs(Knobs &k) {
@@ -84,7 +109,7 @@ int enter(kh_ctx *c, bool flush_pending, bool need_table, bool keep_window, bool
 
 int alloc_table(kh_ctx *c, u64 cap, Slot **out) {
     Slot *t = nullptr;
-    hipError_t e = hipMalloc((void **)&t, cap * sizeof(Slot));
+    hipError_t e = dev_malloc((void **)&t, cap * sizeof(Slot));
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(c, KH_ERR_OOM, "hipMalloc(table)", e);
@@ -109,7 +134,7 @@ int need_table(kh_ctx *c) {
         c->table_dirty = true;
         return KH_OK;
     }
-    hipError_t e = hipMalloc((void **)&c->table, c->cap * sizeof(Slot));
+    hipError_t e = dev_malloc((void **)&c->table, c->cap * sizeof(Slot));
     if (e != hipSuccess) {
         (void)hipGetLastError();
         c->table = nullptr;
@@ -119,7 +144,7 @@ int need_table(kh_ctx *c) {
     return KH_OK;
 }
 void drop_table(kh_ctx *c) {
-    if (c->table && !c->table_borrowed) (void)hipFree(c->table);  // (synchronises the device)
+    if (c->table && !c->table_borrowed) (void)dev_free(c->table);  // (synchronises the device)
     c->table = nullptr;
     c->table_borrowed = false;
 }
@@ -150,7 +175,7 @@ int end_borrow(kh_ctx *c) {
     if (c->table_borrowed && c->table) {  // (rare: a table built by a merge is still wanted while a new count starts, or the buffers go)
         Slot *nt = nullptr;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (hipMalloc((void **)&nt, c->cap * sizeof(Slot)) != hipSuccess) {
+        if (dev_malloc((void **)&nt, c->cap * sizeof(Slot)) != hipSuccess) {
             (void)hipGetLastError();
             return fail(c, KH_ERR_OOM, "hipMalloc(table leaving the partition buffers)");
         }
@@ -167,7 +192,7 @@ int end_borrow(kh_ctx *c) {
 void resize_empty_table(kh_ctx *c, u64 newcap) {
     drop_table(c);
     if (c->ntab) {
-        (void)hipFree(c->ntab);
+        (void)dev_free(c->ntab);
         c->ntab = nullptr;
         c->ntab_cap = 0;
     }
@@ -285,7 +310,7 @@ int grow_to(kh_ctx *c, u64 newcap) {
     if (rc != KH_OK) return rc;
     if (c->ntab) {  // the 8-byte image is for another capacity from here on: its memory is room for the new table
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->ntab);
+        (void)dev_free(c->ntab);
         c->ntab = nullptr;
         c->ntab_cap = 0;
     }
@@ -392,8 +417,8 @@ int release_part_buffers(kh_ctx *c) {
     int brc = end_borrow(c);
     if (brc != KH_OK) return brc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->keysA) (void)hipFree(c->keysA);
-    if (c->keysB) (void)hipFree(c->keysB);
+    if (c->keysA) (void)dev_free(c->keysA);
+    if (c->keysB) (void)dev_free(c->keysB);
     c->keysA = c->keysB = nullptr;
     c->key_cap = c->keyb_cap = 0;
     c->prev_part_budget = c->part_budget;  // (what the context had: it gets it back if the memory is still there, batch.hip ensure_part_budget)
@@ -451,14 +476,17 @@ GeomChoice make_geom(const kh_ctx *c, u64 cap) {
 }
 
 // exclusive scan of `in` (n u32 entries) into `out` (n+1 u64 entries) on the context's stream
-int device_scan(kh_ctx *c, const uint32_t *in, u64 n, u64 *out) {
+int device_scan(kh_ctx *c, const uint32_t *in, u64 n, u64 *out, bool soft, u64 *scratch) {
     const u64 nb = (n + kh::SCAN_CHUNK - 1) / kh::SCAN_CHUNK;
-    int rc = ensure_buf(c, &c->scan_partial, &c->scan_cap, nb + 2, "hipMalloc(scan)");
-    if (rc != KH_OK) return rc;
-    hipLaunchKernelGGL(kh::scan_partials_kernel, dim3((unsigned)nb), dim3(kh::SCAN_NT), 0, c->stream, in, n, c->scan_partial);
-    hipLaunchKernelGGL(kh::scan_spine_kernel, dim3(1), dim3(1024), 0, c->stream, c->scan_partial, nb);
+    if (!scratch) {
+        int rc = ensure_buf(c, &c->scan_partial, &c->scan_cap, nb + 2, "hipMalloc(scan)", soft);
+        if (rc != KH_OK) return rc;
+        scratch = c->scan_partial;
+    }
+    hipLaunchKernelGGL(kh::scan_partials_kernel, dim3((unsigned)nb), dim3(kh::SCAN_NT), 0, c->stream, in, n, scratch);
+    hipLaunchKernelGGL(kh::scan_spine_kernel, dim3(1), dim3(1024), 0, c->stream, scratch, nb);
     hipLaunchKernelGGL(kh::scan_apply_kernel, dim3((unsigned)nb), dim3(kh::SCAN_NT), 0, c->stream, in, n,
-                       (const u64 *)c->scan_partial, out);
+                       (const u64 *)scratch, out);
     HIP_TRY(c, hipGetLastError());
     return KH_OK;
 }
@@ -518,8 +546,8 @@ extern "C" int kh_create(kh_ctx **out, const kh_config *cfg) {
             if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { rc = KH_ERR_HIP; break; }
             c->own_stream = true;
         }
-        if (hipMalloc((void **)&c->d_ctr, sizeof(Counters)) != hipSuccess) { rc = KH_ERR_OOM; break; }
-        if (hipHostMalloc((void **)&c->h_ctr, sizeof(Counters), hipHostMallocDefault) != hipSuccess) { rc = KH_ERR_OOM; break; }
+        if (dev_malloc((void **)&c->d_ctr, sizeof(Counters)) != hipSuccess) { rc = KH_ERR_OOM; break; }
+        if (pin_malloc((void **)&c->h_ctr, sizeof(Counters), hipHostMallocDefault) != hipSuccess) { rc = KH_ERR_OOM; break; }
         if (hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), c->stream) != hipSuccess) { rc = KH_ERR_HIP; break; }
         u64 cap = cfg->capacity_hint ? round_cap((double)cfg->capacity_hint / HINT_LOAD) : DEFAULT_CAP;
         if (const u64 nr = c->knobs.table_regions)  // (test build: a table of exactly this many regions, e.g. 1024 x 40)
@@ -547,8 +575,8 @@ extern "C" void kh_destroy(kh_ctx *c) {
     profile_release(c);
     unitigs_release(c);
     for (int i = 0; i < 2; ++i) {
-        if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
-        if (c->acc[i]) (void)hipFree(c->acc[i]);
+        if (c->h_stage[i]) (void)pin_free(c->h_stage[i]);
+        if (c->acc[i]) (void)dev_free(c->acc[i]);
         if (c->stage_done[i]) (void)hipEventDestroy(c->stage_done[i]);
         if (c->acc_free[i]) (void)hipEventDestroy(c->acc_free[i]);
     }
@@ -558,12 +586,12 @@ extern "C" void kh_destroy(kh_ctx *c) {
                        c->pcount, c->pstart, c->pool_next, c->txt_raw2[0], c->txt_raw2[1], c->txt_acc[0], c->txt_acc[1], c->txt_accq[0], c->txt_accq[1], c->txt_scan_partial, c->txt_ls, c->txt_st,
                        c->txt_tnl, c->txt_tbase, c->txt_tkeep, c->txt_tout, c->txt_err, c->jn_words, c->gr_words};
     for (void *q : scratch)
-        if (q) (void)hipFree(q);
+        if (q) (void)dev_free(q);
     drop_table(c);
-    if (c->ntab) (void)hipFree(c->ntab);
-    if (c->d_ctr) (void)hipFree(c->d_ctr);
-    if (c->h_ctr) (void)hipHostFree(c->h_ctr);
-    if (c->h_txt) (void)hipHostFree(c->h_txt);
+    if (c->ntab) (void)dev_free(c->ntab);
+    if (c->d_ctr) (void)dev_free(c->d_ctr);
+    if (c->h_ctr) (void)pin_free(c->h_ctr);
+    if (c->h_txt) (void)pin_free(c->h_txt);
     for (int i = 0; i < 2; ++i) {
         if (c->txt_acc_done[i]) (void)hipEventDestroy(c->txt_acc_done[i]);
         if (c->txt_copied[i]) (void)hipEventDestroy(c->txt_copied[i]);
@@ -586,6 +614,15 @@ extern "C" int kh_reset(kh_ctx *c) {
         c->win_open = false;
         if (c->win_dirty) c->table_dirty = true;
     }
+    // A poisoning by KH_ERR_OOM or KH_ERR_TABLE_FULL ends here (include/kmerhip.h, "Allocation failures"): the failed call returned
+    // before it launched anything on what it could not allocate, so the streams below drain work on valid memory only, and
+    // every buffer it left half-built is one whose pointer and capacity were zeroed together (ensure_buf, alloc_acc,
+    // ensure_stage) -- the next use allocates it again.  A runtime error (KH_ERR_HIP) stays: nothing is known about the device.
+    const bool revived = c && c->poisoned && c->poisoned_by != KH_ERR_HIP;
+    if (revived) {
+        c->poisoned = false;
+        c->poisoned_by = KH_OK;
+    }
     int rc = enter(c, false, false, false, true);  // (touches no slot: the reset is lazy, and a table nobody has needed yet stays unallocated)
     if (rc != KH_OK) return rc;
     if (c->cstream) HIP_TRY(c, hipStreamSynchronize(c->cstream));
@@ -598,7 +635,7 @@ extern "C" int kh_reset(kh_ctx *c) {
     unitigs_release(c);
     // Lazy: no table_init here (5.5 ms for a 34 GB table).  A partitioned batch into an empty table
     // rewrites every region; any other use clears first (clear_if_dirty).
-    if (!c->table_empty) c->table_dirty = true;
+    if (!c->table_empty || revived) c->table_dirty = true;  // (revived: whatever the failed call wrote before it gave up)
     if (c->table_borrowed) drop_table(c);  // (a merge's table inside the partition buffers: forgotten with its content)
     c->borrow_on = false;
     c->borrow_off[0] = c->borrow_off[1] = 0;
@@ -747,10 +784,10 @@ extern "C" int kh_result_copy(kh_ctx *c, uint64_t *keys, uint64_t *counts, uint6
     } else if (c->borrow_on && (dk = (uint64_t *)borrow(c, need * sizeof(u64))) != nullptr && (dc = (uint64_t *)borrow(c, need * sizeof(u64))) != nullptr) {
         scratch = true;
     } else if ((c->borrow_off[0] = loan0, c->borrow_off[1] = loan1, dk = dc = nullptr, false) ||
-               hipMalloc((void **)&dk, need * sizeof(u64)) != hipSuccess || hipMalloc((void **)&dc, need * sizeof(u64)) != hipSuccess) {
+               dev_malloc((void **)&dk, need * sizeof(u64)) != hipSuccess || dev_malloc((void **)&dc, need * sizeof(u64)) != hipSuccess) {
         (void)hipGetLastError();
-        if (dk) (void)hipFree(dk);
-        return fail(c, KH_ERR_OOM, "hipMalloc(result)");
+        if (dk) (void)dev_free(dk);
+        return soft_oom(c, "hipMalloc(result)");
     }
     uint64_t got = 0;
     rc = kh_result_copy_device(c, dk, dc, need, min_count, &got);
@@ -758,8 +795,8 @@ extern "C" int kh_result_copy(kh_ctx *c, uint64_t *keys, uint64_t *counts, uint6
     if (rc == KH_OK) rc = d2h_staged(c, counts, dc, got * sizeof(u64));
     if (rc == KH_OK) *n = got;
     if (!scratch) {
-        (void)hipFree(dk);
-        (void)hipFree(dc);
+        (void)dev_free(dk);
+        (void)dev_free(dc);
     }
     c->borrow_off[0] = loan0;  // (a loan taken for this call alone goes back)
     c->borrow_off[1] = loan1;
@@ -775,11 +812,11 @@ extern "C" int kh_histogram(kh_ctx *c, uint64_t min_count, uint64_t *count, uint
     u64 big_cap = 1ull << 16;
     std::vector<u64> dense(kh::HIST_DENSE), big;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        if (hipMalloc((void **)&d_dense, kh::HIST_DENSE * sizeof(u64)) != hipSuccess ||
-            hipMalloc((void **)&d_big, big_cap * sizeof(u64)) != hipSuccess) {
+        if (dev_malloc((void **)&d_dense, kh::HIST_DENSE * sizeof(u64)) != hipSuccess ||
+            dev_malloc((void **)&d_big, big_cap * sizeof(u64)) != hipSuccess) {
             (void)hipGetLastError();
-            if (d_dense) (void)hipFree(d_dense);
-            return fail(c, KH_ERR_OOM, "hipMalloc(histogram)");
+            if (d_dense) (void)dev_free(d_dense);
+            return soft_oom(c, "hipMalloc(histogram)");
         }
         rc = zero_cursors(c);
         if (rc == KH_OK && hipMemsetAsync(d_dense, 0, kh::HIST_DENSE * sizeof(u64), c->stream) != hipSuccess)
@@ -801,8 +838,8 @@ extern "C" int kh_histogram(kh_ctx *c, uint64_t min_count, uint64_t *count, uint
                 (nbig && hipMemcpy(big.data(), d_big, nbig * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess))
                 rc = fail(c, KH_ERR_HIP, "hipMemcpy(histogram)");
         }
-        (void)hipFree(d_dense);
-        (void)hipFree(d_big);
+        (void)dev_free(d_dense);
+        (void)dev_free(d_big);
         d_dense = d_big = nullptr;
         if (rc != KH_OK) return rc;
         if (nbig <= big_cap) break;
@@ -832,10 +869,10 @@ extern "C" int kh_lookup(kh_ctx *c, const uint64_t *keys, uint64_t n, uint64_t *
     if (n == 0) return KH_OK;
     if (!keys || !counts) return fail(c, KH_ERR_BAD_ARG, "NULL argument");
     u64 *dk = nullptr, *dc = nullptr;
-    if (hipMalloc((void **)&dk, n * sizeof(u64)) != hipSuccess || hipMalloc((void **)&dc, n * sizeof(u64)) != hipSuccess) {
+    if (dev_malloc((void **)&dk, n * sizeof(u64)) != hipSuccess || dev_malloc((void **)&dc, n * sizeof(u64)) != hipSuccess) {
         (void)hipGetLastError();
-        if (dk) (void)hipFree(dk);
-        return fail(c, KH_ERR_OOM, "hipMalloc(lookup)");
+        if (dk) (void)dev_free(dk);
+        return soft_oom(c, "hipMalloc(lookup)");
     }
     hipError_t e = hipMemcpyAsync(dk, keys, n * sizeof(u64), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
@@ -849,8 +886,8 @@ extern "C" int kh_lookup(kh_ctx *c, const uint64_t *keys, uint64_t n, uint64_t *
     }
     if (e == hipSuccess) e = hipMemcpyAsync(counts, dc, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dk);
-    (void)hipFree(dc);
+    (void)dev_free(dk);
+    (void)dev_free(dc);
     if (e != hipSuccess) return fail(c, KH_ERR_HIP, "kh_lookup", e);
     return KH_OK;
 }
@@ -867,7 +904,7 @@ extern "C" int kh_host_alloc(void **out, uint64_t bytes) {
         return KH_ERR_NO_DEVICE;
     }
     void *p = nullptr;
-    if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocPortable) != hipSuccess) {
+    if (pin_malloc(&p, bytes ? bytes : 1, hipHostMallocPortable) != hipSuccess) {
         (void)hipGetLastError();
         return KH_ERR_OOM;
     }
@@ -877,7 +914,7 @@ extern "C" int kh_host_alloc(void **out, uint64_t bytes) {
 
 extern "C" int kh_host_free(void *p) {
     if (!p) return KH_OK;
-    if (hipHostFree(p) != hipSuccess) {
+    if (pin_free(p) != hipSuccess) {
         (void)hipGetLastError();
         return KH_ERR_BAD_ARG;
     }

@@ -20,7 +20,7 @@ extern "C" int kh_export_by_owner_device(kh_ctx *c, uint32_t nparts, uint64_t *d
     rc = sync_counters(c);
     if (rc != KH_OK) return rc;
     u64 *d_parts = nullptr;
-    if (hipMalloc((void **)&d_parts, nparts * sizeof(u64)) != hipSuccess) {
+    if (dev_malloc((void **)&d_parts, nparts * sizeof(u64)) != hipSuccess) {
         (void)hipGetLastError();
         return fail(c, KH_ERR_OOM, "hipMalloc(parts)");
     }
@@ -41,12 +41,12 @@ extern "C" int kh_export_by_owner_device(kh_ctx *c, uint32_t nparts, uint64_t *d
         part_counts[p] = h[p];
     }
     if (e == hipSuccess && total > cap) {
-        (void)hipFree(d_parts);
+        (void)dev_free(d_parts);
         return fail(c, KH_ERR_RANGE, "export arrays too small");
     }
     if (e == hipSuccess && total) {
         if (!d_keys || !d_counts) {
-            (void)hipFree(d_parts);
+            (void)dev_free(d_parts);
             return fail(c, KH_ERR_BAD_ARG, "NULL output");
         }
         e = hipMemcpyAsync(d_parts, offs.data(), nparts * sizeof(u64), hipMemcpyHostToDevice, c->stream);
@@ -57,7 +57,7 @@ extern "C" int kh_export_by_owner_device(kh_ctx *c, uint32_t nparts, uint64_t *d
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
-    (void)hipFree(d_parts);
+    (void)dev_free(d_parts);
     if (e != hipSuccess) return fail(c, KH_ERR_HIP, "kh_export_by_owner_device", e);
     return KH_OK;
 }
@@ -90,17 +90,17 @@ extern "C" int kh_merge_pairs(kh_ctx *c, const uint64_t *keys, const uint64_t *c
     if (n == 0) return KH_OK;
     if (!keys || !counts) return fail(c, KH_ERR_BAD_ARG, "NULL argument");
     uint64_t *dk = nullptr, *dc = nullptr;
-    if (hipMalloc((void **)&dk, n * sizeof(u64)) != hipSuccess || hipMalloc((void **)&dc, n * sizeof(u64)) != hipSuccess) {
+    if (dev_malloc((void **)&dk, n * sizeof(u64)) != hipSuccess || dev_malloc((void **)&dc, n * sizeof(u64)) != hipSuccess) {
         (void)hipGetLastError();
-        if (dk) (void)hipFree(dk);
+        if (dk) (void)dev_free(dk);
         return fail(c, KH_ERR_OOM, "hipMalloc(merge)");
     }
     hipError_t e = hipMemcpyAsync(dk, keys, n * sizeof(u64), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dc, counts, n * sizeof(u64), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) rc = kh_merge_pairs_device(c, dk, dc, n);
     hipError_t e2 = hipStreamSynchronize(c->stream);
-    (void)hipFree(dk);
-    (void)hipFree(dc);
+    (void)dev_free(dk);
+    (void)dev_free(dc);
     if (e != hipSuccess || e2 != hipSuccess) return fail(c, KH_ERR_HIP, "kh_merge_pairs", e != hipSuccess ? e : e2);
     return rc;
 }
@@ -163,7 +163,7 @@ extern "C" int kh_set_shard(kh_ctx *c, uint32_t index, uint32_t count) {
         }
         if (borrow_room(c) < 16ull * c->cap && (u64)fr < 16ull * (c->cap >> sh) + (8ull << 30)) {  // (round 5: not where the table will be borrowed from the partition buffers)
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            (void)hipFree(c->ntab);
+            (void)dev_free(c->ntab);
             c->ntab = nullptr;
             c->ntab_cap = 0;
         }
@@ -291,7 +291,7 @@ int export_regions(kh_ctx *c, int fmt, uint32_t nparts, void *d_keys, uint64_t *
         // takes the sender's digest of what it writes where the caller wants one
         const kh::SlotSrc ss = slot_src(c);
         u64 *rdig = nullptr;
-        if (d_digest && digest_done && ensure_buf(c, &c->rdig, &c->rdig_cap, 2 * nregions, "hipMalloc(digest partials)") == KH_OK) rdig = c->rdig;
+        if (d_digest && digest_done && ensure_buf(c, &c->rdig, &c->rdig_cap, 2 * nregions, "hipMalloc(digest partials)", true) == KH_OK) rdig = c->rdig;
         if (fmt == XF_HEADS32)
             hipLaunchKernelGGL((kh::region_compact_image_kernel<true>), dim3((unsigned)nregions), dim3(kh::BLOCK), 0, c->stream, ss.ntab, ss.geo, (const u64 *)c->merge_off, c->k,
                                (uint32_t)cb, d_keys, rdig);
@@ -498,11 +498,11 @@ int merge_regions(kh_ctx *c, int fmt, uint32_t nsenders, uint64_t sender_regions
     if (nar && c->ntab_cap != c->cap) {
         if (c->ntab) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            (void)hipFree(c->ntab);
+            (void)dev_free(c->ntab);
             c->ntab = nullptr;
             c->ntab_cap = 0;
         }
-        if (hipMalloc((void **)&c->ntab, c->cap * sizeof(u64)) != hipSuccess) {  // (no room for the image: the 16-byte table it is)
+        if (dev_malloc((void **)&c->ntab, c->cap * sizeof(u64)) != hipSuccess) {  // (no room for the image: the 16-byte table it is)
             (void)hipGetLastError();
             c->ntab = nullptr;
             nar = false;
@@ -603,7 +603,7 @@ int merge_regions(kh_ctx *c, int fmt, uint32_t nsenders, uint64_t sender_regions
             // the arrival digests on the way (exchange.hip): per-workgroup partial sums, folded by a small kernel
             u64 *rdig = nullptr;
             const uint32_t cols = 3 * nsenders;
-            if (d_digest && digest_done && ensure_buf(c, &c->rdig, &c->rdig_cap, (nwin >> K.gshift) * cols, "hipMalloc(digest partials)") == KH_OK) rdig = c->rdig;
+            if (d_digest && digest_done && ensure_buf(c, &c->rdig, &c->rdig_cap, (nwin >> K.gshift) * cols, "hipMalloc(digest partials)", true) == KH_OK) rdig = c->rdig;
             if (fmt == XF_PACKED64)
                 hipLaunchKernelGGL((kh::shard_merge_narrow_kernel<1>), mgn, dim3(kh::SHARD_NT), 0, c->stream, K, a, c->ntab, c->rfail, c->rnew, c->radd, rdig);
             else

@@ -350,8 +350,8 @@ constexpr u64 PF_PAD = 64;                 // behind a chunk's bases: its k - 1 
 // the chunk buffers and events of the two host forms (profile_buffers grows them by releasing them first)
 static void chunk_release(kh_ctx *c) {
     for (int i = 0; i < 2; ++i) {
-        if (c->pf_d[i]) (void)hipFree(c->pf_d[i]);
-        if (c->pf_h[i]) (void)hipHostFree(c->pf_h[i]);
+        if (c->pf_d[i]) (void)dev_free(c->pf_d[i]);
+        if (c->pf_h[i]) (void)pin_free(c->pf_h[i]);
         c->pf_d[i] = c->pf_h[i] = nullptr;
         hipEvent_t *ev[] = {&c->pf_in[i], &c->pf_run[i], &c->pf_out[i]};
         for (hipEvent_t *e : ev) {
@@ -364,8 +364,8 @@ static void chunk_release(kh_ctx *c) {
 
 void profile_release(kh_ctx *c) {
     chunk_release(c);
-    if (c->pr_rows) (void)hipFree(c->pr_rows);
-    if (c->pr_rec) (void)hipFree(c->pr_rec);
+    if (c->pr_rows) (void)dev_free(c->pr_rows);
+    if (c->pr_rec) (void)dev_free(c->pr_rec);
     c->pr_rows = nullptr;
     c->pr_rec = nullptr;
     c->pr_rows_cap = c->pr_rec_cap = 0;
@@ -438,12 +438,12 @@ int profile_buffers(kh_ctx *c, u64 chunk) {
         chunk_release(c);
         const u64 bytes = 2 * pf_in_stride(chunk) + 4 * chunk;
         for (int i = 0; i < 2; ++i) {
-            hipError_t e = hipMalloc((void **)&c->pf_d[i], bytes);
-            if (e == hipSuccess) e = hipHostMalloc((void **)&c->pf_h[i], bytes, hipHostMallocDefault);
+            hipError_t e = dev_malloc((void **)&c->pf_d[i], bytes);
+            if (e == hipSuccess) e = pin_malloc((void **)&c->pf_h[i], bytes, hipHostMallocDefault);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 chunk_release(c);
-                return fail(c, KH_ERR_OOM, "kh_profile: chunk buffers", e);
+                return soft_oom(c, "kh_profile: chunk buffers", e);  // (a reading call: the context stays usable)
             }
         }
         c->pf_chunk = chunk;
@@ -472,19 +472,19 @@ int records_finalize(kh_ctx *c, uint32_t *d_rows, u64 nrec, int sumw) {
 int records_buffers(kh_ctx *c, u64 nrec) {
     if (c->pr_rows_cap >= nrec && c->pr_rec_cap >= nrec + 1) return KH_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->pr_rows) (void)hipFree(c->pr_rows);
-    if (c->pr_rec) (void)hipFree(c->pr_rec);
+    if (c->pr_rows) (void)dev_free(c->pr_rows);
+    if (c->pr_rec) (void)dev_free(c->pr_rec);
     c->pr_rows = nullptr;
     c->pr_rec = nullptr;
     c->pr_rows_cap = c->pr_rec_cap = 0;
-    hipError_t e = hipMalloc((void **)&c->pr_rows, nrec * KH_REC_WORDS * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->pr_rec, (nrec + 1) * sizeof(u64));
+    hipError_t e = dev_malloc((void **)&c->pr_rows, nrec * KH_REC_WORDS * sizeof(uint32_t));
+    if (e == hipSuccess) e = dev_malloc((void **)&c->pr_rec, (nrec + 1) * sizeof(u64));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        if (c->pr_rows) (void)hipFree(c->pr_rows);
+        if (c->pr_rows) (void)dev_free(c->pr_rows);
         c->pr_rows = nullptr;
         c->pr_rec = nullptr;
-        return fail(c, KH_ERR_OOM, "kh_profile_records: row buffers", e);
+        return soft_oom(c, "kh_profile_records: row buffers", e);  // (a reading call: the context stays usable)
     }
     c->pr_rows_cap = nrec;
     c->pr_rec_cap = nrec + 1;

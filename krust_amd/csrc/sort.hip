@@ -10,15 +10,6 @@
 
 namespace khi {
 
-namespace {
-
-int soft_oom(kh_ctx *c, const char *what) {  // (not fail(): an allocation of this call alone failed, the table is untouched)
-    c->last_error = what;
-    return KH_ERR_OOM;
-}
-
-}  // namespace
-
 SortScratch::SortScratch(kh_ctx *ctx) : c(ctx), loan0(ctx->borrow_off[0]), loan1(ctx->borrow_off[1]) {}
 
 void *SortScratch::take(u64 bytes) {
@@ -36,14 +27,14 @@ void *SortScratch::take(u64 bytes) {
         return p;
     }
     void *p = nullptr;
-    if (hipMalloc(&p, need) != hipSuccess) {
+    if (dev_malloc(&p, need) != hipSuccess) {
         (void)hipGetLastError();
         return nullptr;
     }
     try {
         owned.push_back(p);
     } catch (...) {
-        (void)hipFree(p);
+        (void)dev_free(p);
         return nullptr;
     }
     return p;
@@ -51,7 +42,7 @@ void *SortScratch::take(u64 bytes) {
 
 SortScratch::~SortScratch() {
     if (!owned.empty()) (void)hipStreamSynchronize(c->stream);
-    for (void *p : owned) (void)hipFree(p);
+    for (void *p : owned) (void)dev_free(p);
     c->borrow_off[0] = loan0;  // (a loan taken for this call alone goes back)
     c->borrow_off[1] = loan1;
 }
@@ -66,7 +57,8 @@ int sorted_into(kh_ctx *c, u64 *out_keys, u64 *out_counts, u64 n, u64 min_count,
     u64 *const tc = (u64 *)sc.take(n * sizeof(u64));
     uint32_t *const hist = (uint32_t *)sc.take(nhist * sizeof(uint32_t));
     u64 *const start = (u64 *)sc.take((nhist + 1) * sizeof(u64));
-    if (!tk || !tc || !hist || !start) return soft_oom(c, "device memory for the sort's scratch");
+    u64 *const scan = (u64 *)sc.take(device_scan_scratch(nhist));  // (not the context's: nothing of this call stays allocated)
+    if (!tk || !tc || !hist || !start || !scan) return soft_oom(c, "device memory for the sort's scratch");
     const uint32_t passes = kh::sort_passes(c->k);
     u64 *k0 = (passes & 1u) ? tk : out_keys, *c0 = (passes & 1u) ? tc : out_counts;  // an odd number of passes ends in the other pair
     u64 *k1 = (passes & 1u) ? out_keys : tk, *c1 = (passes & 1u) ? out_counts : tc;
@@ -83,7 +75,7 @@ int sorted_into(kh_ctx *c, u64 *out_keys, u64 *out_counts, u64 n, u64 min_count,
             s += m;
         }
         HIP_TRY(c, hipGetLastError());
-        if ((rc = device_scan(c, hist, nhist, start)) != KH_OK) return rc;
+        if ((rc = device_scan(c, hist, nhist, start, true, scan)) != KH_OK) return rc;
         for (u64 s = 0; s < ntiles;) {
             const u64 m = std::min<u64>(ntiles - s, 1ull << 30);
             hipLaunchKernelGGL(kh::sort_scatter_kernel, dim3((unsigned)m), dim3(kh::BLOCK), 0, c->stream, (const u64 *)k0, (const u64 *)c0,

@@ -565,18 +565,13 @@ KH_GLOBAL __launch_bounds__(BLOCK) void clip_keep_kernel(TableGeom tg, u64 q0, u
 namespace khi {
 
 void unitigs_release(kh_ctx *c) {
-    if (c->un.rows) (void)hipFree(c->un.rows);  // (synchronises the device)
-    if (c->un.bases) (void)hipFree(c->un.bases);
-    if (c->un.links) (void)hipFree(c->un.links);
+    if (c->un.rows) (void)dev_free(c->un.rows);  // (synchronises the device)
+    if (c->un.bases) (void)dev_free(c->un.bases);
+    if (c->un.links) (void)dev_free(c->un.links);
     c->un = kh_ctx::Unitigs();
 }
 
 namespace {
-
-int soft_oom(kh_ctx *c, const char *what) {  // (not fail(): an allocation of this call alone failed, the table is untouched)
-    c->last_error = what;
-    return KH_ERR_OOM;
-}
 
 unsigned uni_grid(u64 items) { return (unsigned)grid_for(items); }
 
@@ -673,7 +668,8 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJo
     uint32_t *const rank = (uint32_t *)sc.take(6 * states * sizeof(uint32_t));
     u64 *const uidx = (u64 *)sc.take((n + 1) * sizeof(u64));
     uint32_t *const d_flag = (uint32_t *)sc.take(2 * sizeof(uint32_t));  // "something changed", "something is inconsistent"
-    if (!slot2id || !masks || !circ || !next || !rank || !uidx || !d_flag) return soft_oom(c, "device memory for the unitigs' scratch");
+    u64 *const scan = (u64 *)sc.take(device_scan_scratch(2 * n));  // for the scans below, of n, nu <= n and 2 nu entries (not the context's scratch: nothing of this call stays allocated)
+    if (!slot2id || !masks || !circ || !next || !rank || !uidx || !d_flag || !scan) return soft_oom(c, "device memory for the unitigs' scratch");
     kh::UniRank cur{rank, rank + states, rank + 2 * states}, oth{rank + 3 * states, rank + 4 * states, rank + 5 * states};
     HIP_TRY(c, hipMemsetAsync(slot2id, 0xFF, c->cap * sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(circ, 0, n, c->stream));
@@ -707,7 +703,7 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJo
     hipLaunchKernelGGL(kh::unitig_reading_kernel, dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const uint32_t *)next, n32, cur, head, posg, first,
                        d_flag + 1);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = device_scan(c, first, n, uidx)) != KH_OK) return rc;
+    if ((rc = device_scan(c, first, n, uidx, true, scan)) != KH_OK) return rc;
     u64 nu = 0;
     HIP_TRY(c, hipMemcpyAsync(&nu, uidx + n, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -716,7 +712,7 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJo
     uint32_t *const ulen = (uint32_t *)sc.take(nu * sizeof(uint32_t));
     u64 *const ustart = (u64 *)sc.take((nu + 1) * sizeof(u64));
     if (!ulen || !ustart) return soft_oom(c, "device memory for the unitigs' offsets");
-    if (hipMalloc((void **)&c->un.rows, nu * KH_UNI_WORDS * sizeof(u64)) != hipSuccess) {
+    if (dev_malloc((void **)&c->un.rows, nu * KH_UNI_WORDS * sizeof(u64)) != hipSuccess) {
         (void)hipGetLastError();
         c->un.rows = nullptr;
         return soft_oom(c, "hipMalloc(unitig rows)");
@@ -724,12 +720,12 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJo
     hipLaunchKernelGGL(kh::unitig_row_kernel, dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, n32, k, cur, (const uint32_t *)first, (const u64 *)uidx,
                        (const uint8_t *)circ, nu, ulen, c->un.rows);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = device_scan(c, ulen, nu, ustart)) != KH_OK) return rc;
+    if ((rc = device_scan(c, ulen, nu, ustart, true, scan)) != KH_OK) return rc;
     u64 nb = 0;
     HIP_TRY(c, hipMemcpyAsync(&nb, ustart + nu, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (nb != n + nu * (k - 1)) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: the unitigs' lengths do not add up (internal error)");
-    if (!clip && hipMalloc((void **)&c->un.bases, nb) != hipSuccess) {
+    if (!clip && dev_malloc((void **)&c->un.bases, nb) != hipSuccess) {
         (void)hipGetLastError();
         c->un.bases = nullptr;
         return soft_oom(c, "hipMalloc(unitig bases)");
@@ -752,7 +748,7 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJo
         hipLaunchKernelGGL(kh::unitig_end_degree_kernel, dim3(uni_grid(2 * nu)), dim3(kh::BLOCK), 0, c->stream, n32, k, nu, (const u64 *)c->un.rows,
                            (const uint32_t *)order, (const uint8_t *)masks, deg, d_flag + 1);
         HIP_TRY(c, hipGetLastError());
-        if ((rc = device_scan(c, deg, 2 * nu, loff)) != KH_OK) return rc;
+        if ((rc = device_scan(c, deg, 2 * nu, loff, true, scan)) != KH_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(&nl, loff + 2 * nu, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     }
     uint32_t bad = 0;
@@ -761,7 +757,7 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJo
     if (bad) return fail(c, KH_ERR_STATE, "kh_unitigs_begin: the chains are inconsistent (internal error)");
     if (nl > 8 * nu) return fail(c, KH_ERR_STATE, "kh_unitigs_begin_linked: the end states' degrees do not add up (internal error)");
     if (nl) {
-        if (hipMalloc((void **)&c->un.links, nl * sizeof(u64)) != hipSuccess) {
+        if (dev_malloc((void **)&c->un.links, nl * sizeof(u64)) != hipSuccess) {
             (void)hipGetLastError();
             c->un.links = nullptr;
             return soft_oom(c, "hipMalloc(unitig links)");

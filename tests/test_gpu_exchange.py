@@ -358,10 +358,20 @@ def test_a_rank_whose_context_is_poisoned_joins_the_first_gather(K, monkeypatch)
     with K.DeviceGroup(21, [0, 0, 0], capacity_hint=1_000_000) as g:
         for dc in g.counters:
             dc.push(bases)
-        # poison rank 1: an 8 TB device allocation (kh_lookup of 2^40 keys; fails before a single key is read)
-        one = (C.c_uint64 * 1)(0)
-        rc = L.kh_lookup(g[1]._h, one, C.c_uint64(1 << 40), one)
+        # poison rank 1: the counting that its push left pending runs out of memory (KMERHIP_ALLOC_FAIL, the test build's injected
+        # allocation failure: from the first allocation on, every one fails)
+        monkeypatch.setenv("KMERHIP_ALLOC_FAIL", "1+")
+        rc = L.kh_finish(g[1]._h, None)
+        monkeypatch.delenv("KMERHIP_ALLOC_FAIL")
         assert rc == K.native.KH_ERR_OOM
+        assert L.kh_result_size(g[1]._h, 1, C.byref(C.c_uint64(0))) == K.native.KH_ERR_STATE
+        # a reading call that cannot have its scratch -- an 8 TB device allocation: kh_lookup of 2^40 keys, which fails before a
+        # single key is read -- is KH_ERR_OOM and poisons nothing (include/kmerhip.h, "Allocation failures"): rank 0 stays usable
+        one = (C.c_uint64 * 1)(0)
+        rc = L.kh_lookup(g[0]._h, one, C.c_uint64(1 << 40), one)
+        assert rc == K.native.KH_ERR_OOM and b"hipMalloc(lookup)" in L.kh_last_error(g[0]._h)
+        size = C.c_uint64(0)
+        assert L.kh_result_size(g[0]._h, 1, C.byref(size)) == K.native.KH_OK and size.value > 0
         t0 = time.time()
         res = _merge_each_rank_on_its_own_thread(K, g)
         assert time.time() - t0 < 30, "the ranks left, but only after a time-out"
