@@ -1,7 +1,7 @@
 // ctx.hip.h -- what the translation units behind include/kmerhip.h share: the context, its constants and knobs, and the
 // helpers one unit defines for the others.
 //
-//   kmerhip.hip   life cycle, table management (lazy allocation, growth, the 8-byte image), results, host memory, pure helpers
+//   kmerhip.hip   life cycle, enter(), table management (lazy allocation, growth, the 8-byte image), a call's scratch, results, host memory, pure helpers
 //   batch.hip     counting one device-resident range: the direct path and the partitioned batch (level 1 -> level 2 -> regions)
 //   input.hip     kh_push* / kh_push_text*: staging, device accumulation, record scanning
 //   merge.hip     exports and merges of one context (pairs, dense, region-ordered)
@@ -13,6 +13,10 @@
 //   sort.hip      kh_result_sorted*: the result pairs in ascending key order (a device radix sort; format.hip streams it as text)
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
+//
+// Two things every unit does the same way, declared once below: a call ENTERS the context through enter() with one of the named
+// Entry presets (ENTER_WRITE, ENTER_READ, ...: what is counted, widened, cleared and ended on the way in), and device memory that
+// lives for one call is a CallScratch, whose destructor is its only release.
 //
 // Everything here is hidden: the library is built with -fvisibility=hidden and linked with kmerhip.map, so it exports the kh_*
 // entry points of include/kmerhip.h only (tests/test_abi.py holds `nm -D` to that list).
@@ -348,7 +352,7 @@ struct kh_ctx {
     // begin sizes every tile of FMT_TILE slots (records, bytes) and scans both; next formats ranges of whole tiles into one of two
     // device chunks -- the idle partition buffers where there are any, else small buffers of the stream's own -- and hands their text
     // out record-aligned: chunk i + 1 is formatted on `stream` while chunk i travels on `cstream`.  `on` falls with every call
-    // that enters the context for anything but reading (enter(), reader = false).
+    // that enters the context for anything but reading (enter(), Entry::reader).
     struct TextStream {
         bool on = false;
         uint32_t format = 0;
@@ -390,7 +394,7 @@ struct kh_ctx {
     // kh_graph_stats (graph.hip): the KH_GRAPH_WORDS words its kernel adds up
     u64 *gr_words = nullptr;
     // kh_unitigs_* (unitig.hip): the rows, bases and links of the last kh_unitigs_begin[_linked], memory of the context's own until kh_unitigs_end /
-    // the next begin / kh_reset / kh_destroy.  `live` falls with every call that enters as a writer (enter(), reader = false).
+    // the next begin / kh_reset / kh_destroy.  `live` falls with every call that enters for anything but reading (enter(), Entry::reader).
     struct Unitigs {
         bool live = false;
         u64 *rows = nullptr;      // KH_UNI_WORDS words per unitig
@@ -448,10 +452,37 @@ inline int grid_for(u64 items) {
 
 // ---- kmerhip.hip -----------------------------------------------------------------------------------------------------------
 // Every entry point starts with enter(): host pushes are accumulated on the device and counted lazily; anything that looks at
-// the table first counts what is pending.
-// reader: the call only reads the table (a text stream in progress survives it: kh_result_text_next).
-int enter(kh_ctx *c, bool flush_pending = true, bool need_table = true, bool keep_window = false, bool narrow_ok = false,
-          bool reader = false);
+// the table first counts what is pending.  What a call needs of the context on its way in is an Entry: one of the presets
+// below, or -- kh_set_shard, export_regions, merge_regions -- a preset with one field changed where the call is made.
+struct Entry {
+    bool flush_pending = true;  // what kh_push / kh_push_text left pending is counted first
+    bool need_table = true;     // the 16-byte table exists and, if lazily reset, is cleared (unless the 8-byte image holds the counts)
+    bool keep_window = false;   // a fresh merge in pieces (kh_set_region_window) stays open: this call merges its next piece
+    bool narrow_ok = false;     // the 8-byte image stays what it is (false: widened into the 16-byte table first)
+    bool reader = false;        // the call only reads the table: a text stream in progress and the unitigs of kh_unitigs_begin survive it
+};
+// The pair and dense merges, the exports by owner, kh_comm_init, the dst of kh_combine_into / kh_clip_tips_into: a cleared
+// 16-byte table, everything pending counted, whatever hangs on the table's content (text stream, unitigs, merge window) ended.
+constexpr Entry ENTER_WRITE{};
+// kh_finish, kh_result_size, kh_histogram, kh_lookup, kh_profile*, the sources of kh_compare / kh_combine_into, kh_graph_*,
+// the copies of the unitigs, kh_result_text_begin: everything pending counted, the table in the form it is in, nothing ended.
+constexpr Entry ENTER_READ{true, true, false, true, true};
+// kh_result_copy*, kh_result_sorted*, kh_region_unit_counts_device, kh_unitigs_begin*, the src of kh_clip_tips_into,
+// kh_merge_across: reads the table in the form it is in, but may take the idle partition buffers -- a text stream, whose chunks
+// live there, ends (and with it the unitigs).
+constexpr Entry ENTER_READ_TAKE{true, true, false, true, false};
+// kh_push, kh_push_text, kh_reset: touches no slot and counts nothing -- the push is accumulated beside what is pending, a lazily
+// reset table stays lazily reset and one nobody has needed yet stays unallocated.
+constexpr Entry ENTER_PUSH{false, false, false, true, false};
+// kh_push_device, kh_push_text_device: as ENTER_PUSH, with what is pending counted first (the resident range is counted at once,
+// behind it; the counting path decides by itself which form of the table it needs).
+constexpr Entry ENTER_PUSH_DEVICE{true, false, false, true, false};
+// kh_result_text_next*: the next piece of the stream that kh_result_text_begin sized -- nothing is counted, nothing ended.
+constexpr Entry ENTER_TEXT_NEXT{false, false, false, true, true};
+int enter(kh_ctx *c, Entry how = ENTER_WRITE);
+// What kh_result_copy, kh_result_sorted and kh_result_sorted_device do first: enter, *n = 0, *need = the pairs with
+// count >= min_count, KH_ERR_RANGE when that is more than cap.  (KH_OK with *need == 0: nothing to copy.)
+int result_enter(kh_ctx *c, const void *keys, const void *counts, u64 cap, u64 min_count, uint64_t *n, uint64_t *need);
 int need_table(kh_ctx *c);
 void resize_empty_table(kh_ctx *c, u64 newcap);
 int clear_if_dirty(kh_ctx *c);
@@ -471,8 +502,25 @@ void *borrow(kh_ctx *c, u64 bytes);   // `bytes` of the idle partition buffers (
 u64 borrow_room(const kh_ctx *c);     // the largest single request borrow() could serve now
 int end_borrow(kh_ctx *c);            // the partition buffers are about to be written (or freed): a borrowed table moves to memory of its own
 void drop_table(kh_ctx *c);           // the 16-byte table is no longer needed: freed, unless it was borrowed
+// Device memory for the length of one call.  Two ways to have some, both nullptr when there is none -- the caller says soft_oom()
+// or fail(KH_ERR_OOM): take(), from the idle partition buffers when nothing is borrowed, else from borrow(), else fresh();
+// fresh(), a new allocation of exactly `bytes`, whatever lies idle.  The destructor is the only place that gives anything back:
+// it drains the context's stream if the call owns an allocation, frees, and ends the loans the call took.
+struct CallScratch {
+    kh_ctx *c;
+    u64 loan0, loan1;
+    bool lent = false;
+    u64 used[2] = {0, 0};
+    std::vector<void *> owned;
+    explicit CallScratch(kh_ctx *ctx);
+    ~CallScratch();
+    CallScratch(const CallScratch &) = delete;
+    CallScratch &operator=(const CallScratch &) = delete;
+    void *take(u64 bytes);
+    void *fresh(u64 bytes);
+};
 // soft: the context's scan scratch fails as a reading call's (ensure_buf).  scratch: device_scan_scratch(n) bytes of the caller's own to
-// use instead -- the calls that promise to leave nothing allocated (sort.hip, unitig.hip) take them from their SortScratch.
+// use instead -- the calls that promise to leave nothing allocated (sort.hip, unitig.hip) take them from their CallScratch.
 int device_scan(kh_ctx *c, const uint32_t *in, u64 n, u64 *out, bool soft = false, u64 *scratch = nullptr);
 inline u64 device_scan_scratch(u64 n) { return ((n + kh::SCAN_CHUNK - 1) / kh::SCAN_CHUNK + 2) * sizeof(u64); }
 int zero_cursors(kh_ctx *c);
@@ -510,20 +558,7 @@ void comm_release(kh_ctx *c);
 // ---- format.hip
 void text_release(kh_ctx *c);  // kh_destroy: the text stream's buffers and events
 // ---- sort.hip
-// Device memory for the length of one call: the idle partition buffers when nothing is borrowed, else borrow(), else hipMalloc.
-// take() returns nullptr when there is none (the context stays usable); the destructor gives everything back.
-struct SortScratch {
-    kh_ctx *c;
-    u64 loan0, loan1;
-    u64 used[2] = {0, 0};
-    std::vector<void *> owned;
-    explicit SortScratch(kh_ctx *ctx);
-    ~SortScratch();
-    SortScratch(const SortScratch &) = delete;
-    SortScratch &operator=(const SortScratch &) = delete;
-    void *take(u64 bytes);
-};
-int sorted_into(kh_ctx *c, u64 *out_keys, u64 *out_counts, u64 n, u64 min_count, SortScratch &sc);
+int sorted_into(kh_ctx *c, u64 *out_keys, u64 *out_counts, u64 n, u64 min_count, CallScratch &sc);
 // ---- join.hip
 // What the table-against-table calls refuse before they enter anything (b, dst may be nullptr): `err` takes the text.
 int join_check(kh_ctx *err, const char *who, const kh_ctx *a, const kh_ctx *b, const kh_ctx *dst);

@@ -1311,7 +1311,7 @@ extern "C" int kh_merge_across(kh_ctx *c, kh_merge_info *info) {
     // (counts what kh_push / kh_push_text left pending: may fail -- out of memory, table full -- on this rank alone.  The 8-byte
     //  image stays what it is: the exports read it directly -- round 4: the default here widened it first, 13.5 ms and a 43 GB
     //  allocation at configs[3]'s size, and every export then read the 16-byte table)
-    int rc = enter(c, true, true, false, true);
+    int rc = enter(c, ENTER_READ_TAKE);
     if (c->comm && c->comm->nranks > 1) return merge_across_impl(c, info, rc);  // a failed pre-check is reported in the first gather
     if (rc != KH_OK) return rc;
     if (!c->comm) {  // a lone context is its own world

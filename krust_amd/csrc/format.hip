@@ -126,7 +126,7 @@ int cut_at_record(kh_ctx *c, const kh_ctx::TextStream::Chunk &ch, u64 room, u64 
 }
 
 int text_next(kh_ctx *c, uint8_t *buf, u64 cap, u64 *n, bool to_device) {
-    int rc = enter(c, false, false, false, true, true);
+    int rc = enter(c, ENTER_TEXT_NEXT);
     if (rc != KH_OK) return rc;
     if (!n || (cap && !buf)) return fail(c, KH_ERR_BAD_ARG, "NULL output");
     *n = 0;
@@ -197,7 +197,7 @@ int text_next(kh_ctx *c, uint8_t *buf, u64 cap, u64 *n, bool to_device) {
 using namespace khi;
 
 extern "C" int kh_result_text_begin(kh_ctx *c, uint32_t format, uint64_t min_count, uint64_t *n_records, uint64_t *n_bytes) {
-    int rc = enter(c, true, true, false, true, true);
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     auto &ts = c->ts;
     ts.on = false;
@@ -211,7 +211,7 @@ extern "C" int kh_result_text_begin(kh_ctx *c, uint32_t format, uint64_t min_cou
         if ((rc = kh_result_size(c, min_count, &sorted_n)) != KH_OK) return rc;
         if ((rc = ensure_buf(c, &c->ts_skey, &c->ts_skey_cap, std::max<u64>(sorted_n, 1), "hipMalloc(sorted text pairs)", true)) != KH_OK) return rc;
         if ((rc = ensure_buf(c, &c->ts_scnt, &c->ts_scnt_cap, std::max<u64>(sorted_n, 1), "hipMalloc(sorted text pairs)", true)) != KH_OK) return rc;
-        SortScratch sc(c);
+        CallScratch sc(c);
         if ((rc = sorted_into(c, c->ts_skey, c->ts_scnt, sorted_n, min_count, sc)) != KH_OK) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }

@@ -146,24 +146,21 @@ namespace {
 // What all three calls do before they look at the table: neighbours of a shard's keys live on other owners.
 int graph_enter(kh_ctx *c, const char *who) {
     if (c->shard_shift) return fail(c, KH_ERR_STATE, (std::string(who) + ": the table is a shard; its k-mers' neighbours live on other owners").c_str());
-    return enter(c, true, true, false, true, true);  // a reader: pending pushes counted, the table in the form it is in
+    return enter(c, ENTER_READ);
 }
 
 // One launch of graph_kernel on c's stream: the source against c's own table in the form it is in.
 template <typename SRC, typename SINK>
 int graph_launch_on(kh_ctx *c, SRC sv, u64 s0, u64 s1, u64 groups, u64 min_count, SINK sink, uint32_t shift) {
     const unsigned blocks = (unsigned)std::min<u64>(groups, (u64)grid_cap());
-    // (a slot source is the context's own table: only the probe of the same form is instantiated with it)
-    if constexpr (!std::is_same<SRC, kh::JsWide>::value) {
-        if (c->narrow)
-            hipLaunchKernelGGL((kh::graph_kernel<SRC, kh::PfNarrow, SINK>), dim3(blocks), dim3(kh::BLOCK), 0, c->stream, sv, s0, s1, c->k, min_count,
-                               kh::PfNarrow{(const u64 *)c->ntab, c->narrow_g}, sink, shift);
-    }
-    if constexpr (!std::is_same<SRC, kh::JsNarrow>::value) {
-        if (!c->narrow)
-            hipLaunchKernelGGL((kh::graph_kernel<SRC, kh::PfWide, SINK>), dim3(blocks), dim3(kh::BLOCK), 0, c->stream, sv, s0, s1, c->k, min_count,
-                               kh::PfWide{table_geom(c, c->table, c->cap)}, sink, shift);
-    }
+    with_probe(c, [&](auto pv) {
+        typedef decltype(pv) PRB;
+        // (a slot source is the context's own table: only the probe of the same form is instantiated with it)
+        constexpr bool other_form = (std::is_same<SRC, kh::JsWide>::value && std::is_same<PRB, kh::PfNarrow>::value) ||
+                                    (std::is_same<SRC, kh::JsNarrow>::value && std::is_same<PRB, kh::PfWide>::value);
+        if constexpr (!other_form)
+            hipLaunchKernelGGL((kh::graph_kernel<SRC, PRB, SINK>), dim3(blocks), dim3(kh::BLOCK), 0, c->stream, sv, s0, s1, c->k, min_count, pv, sink, shift);
+    });
     HIP_TRY(c, hipGetLastError());
     return KH_OK;
 }
@@ -198,8 +195,7 @@ extern "C" int kh_graph_stats(kh_ctx *c, uint64_t min_count, uint64_t *out) {
     if (c->cap) {
         const u64 ntiles = (c->cap + kh::GRAPH_TILE - 1) / kh::GRAPH_TILE;
         const kh::GkStats sink{c->gr_words};
-        if (c->narrow) rc = graph_launch_on(c, kh::JsNarrow{(const u64 *)c->ntab, c->narrow_g}, 0, c->cap, ntiles, mc, sink, 0);
-        else rc = graph_launch_on(c, kh::JsWide{(const Slot *)c->table}, 0, c->cap, ntiles, mc, sink, 0);
+        with_source(c, [&](auto sv) { rc = graph_launch_on(c, sv, 0, c->cap, ntiles, mc, sink, 0); });
         if (rc != KH_OK) return rc;
     }
     u64 words[KH_GRAPH_WORDS];
@@ -225,22 +221,17 @@ extern "C" int kh_graph_masks(kh_ctx *c, const uint64_t *keys, uint64_t n, uint6
     int rc = graph_enter(c, "kh_graph_masks");
     if (rc != KH_OK || n == 0) return rc;
     // as kh_lookup: device scratch for this call alone, one launch, copy back
-    u64 *dk = nullptr;
-    uint8_t *dm = nullptr;
-    if (n > (~0ull >> 4) || dev_malloc((void **)&dk, n * sizeof(u64)) != hipSuccess || dev_malloc((void **)&dm, n) != hipSuccess) {
-        (void)hipGetLastError();
-        if (dk) (void)dev_free(dk);
-        return soft_oom(c, "hipMalloc(graph masks)");
-    }
+    CallScratch sc(c);
+    u64 *const dk = n > (~0ull >> 4) ? nullptr : (u64 *)sc.fresh(n * sizeof(u64));
+    uint8_t *const dm = dk ? (uint8_t *)sc.fresh(n) : nullptr;
+    if (!dm) return soft_oom(c, "hipMalloc(graph masks)");
     hipError_t e = hipMemcpyAsync(dk, keys, n * sizeof(u64), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         rc = graph_masks_launch(c, dk, n, min_count ? min_count : 1, dm);
         if (rc == KH_OK) e = hipMemcpyAsync(masks, dm, n, hipMemcpyDeviceToHost, c->stream);
     }
-    const hipError_t es = hipStreamSynchronize(c->stream);  // (before the scratch is freed, whatever happened)
+    const hipError_t es = hipStreamSynchronize(c->stream);  // (an error of the stream is this call's to report, not the scratch's)
     if (e == hipSuccess) e = es;
-    (void)dev_free(dk);
-    (void)dev_free(dm);
     if (rc != KH_OK) return rc;
     if (e != hipSuccess) return fail(c, KH_ERR_HIP, "kh_graph_masks", e);
     return KH_OK;

@@ -229,7 +229,7 @@ using namespace khi;
 // input
 // =============================================================================================
 extern "C" int kh_push_device(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, uint64_t n) {
-    int rc = enter(c, true, false, false, true);
+    int rc = enter(c, ENTER_PUSH_DEVICE);
     if (rc != KH_OK) return rc;
     if (n && !d_bases) return fail(c, KH_ERR_BAD_ARG, "d_bases is NULL");
     if (c->shard_shift) return fail(c, KH_ERR_STATE, "a shard table only accepts kh_merge_*; kh_reset makes it a full table again");
@@ -239,7 +239,7 @@ extern "C" int kh_push_device(kh_ctx *c, const uint8_t *d_bases, const uint8_t *
 }
 
 extern "C" int kh_push(kh_ctx *c, const uint8_t *bases, const uint8_t *qual, uint64_t n) {
-    int rc = enter(c, false, false, false, true);
+    int rc = enter(c, ENTER_PUSH);
     if (rc != KH_OK) return rc;
     if (n && !bases) return fail(c, KH_ERR_BAD_ARG, "bases is NULL");
     if (c->shard_shift) return fail(c, KH_ERR_STATE, "a shard table only accepts kh_merge_*; kh_reset makes it a full table again");
@@ -580,7 +580,7 @@ int text_args(kh_ctx *c, const uint8_t *text, u64 n, int format) {
 }  // namespace khi
 
 extern "C" int kh_push_text_device(kh_ctx *c, const uint8_t *d_text, uint64_t n, int format) {
-    int rc = enter(c, true, false, false, true);
+    int rc = enter(c, ENTER_PUSH_DEVICE);
     if (rc != KH_OK) return rc;
     if ((rc = text_args(c, d_text, n, format)) != KH_OK) return rc;
     if (n == 0) return KH_OK;
@@ -611,7 +611,7 @@ int scan_unscanned(kh_ctx *c) {
 extern "C" int kh_push_text(kh_ctx *c, const uint8_t *text, uint64_t n, int format) {
     // (what earlier calls have accumulated stays where it is: it is counted when its buffer is full, or by whatever looks
     //  at the table next)
-    int rc = enter(c, false, false, false, true);
+    int rc = enter(c, ENTER_PUSH);
     if (rc != KH_OK) return rc;
     if ((rc = text_args(c, text, n, format)) != KH_OK) return rc;
     if (n == 0) return KH_OK;

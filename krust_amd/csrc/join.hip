@@ -184,28 +184,22 @@ int join_launch(kh_ctx *on, const kh_ctx *src, u64 s0, u64 s1, u64 min_src, cons
     if (s1 <= s0) return KH_OK;
     const u64 ntiles = (s1 - s0 + (u64)kh::JOIN_PER * kh::BLOCK - 1) / ((u64)kh::JOIN_PER * kh::BLOCK);
     const unsigned blocks = (unsigned)std::min<u64>(ntiles, (u64)grid_cap());
-    auto with_probe = [&](auto sv) {
+    with_source(src, [&](auto sv) {
         typedef decltype(sv) SRC;
         auto go = [&](auto pv) {
             typedef decltype(pv) PRB;
             hipLaunchKernelGGL((kh::join_kernel<SRC, PRB, SINK>), dim3(blocks), dim3(kh::BLOCK), 0, on->stream, sv, s0, s1, min_src, pv, min_prb, sink);
         };
-        if constexpr (std::is_same<SINK, kh::JkStats<true>>::value) {
-            go(kh::PbNone{});
-        } else {
-            if (prb->narrow) go(kh::PfNarrow{(const u64 *)prb->ntab, prb->narrow_g});
-            else go(kh::PfWide{table_geom(prb, prb->table, prb->cap)});
-        }
-    };
-    if (src->narrow) with_probe(kh::JsNarrow{(const u64 *)src->ntab, src->narrow_g});
-    else with_probe(kh::JsWide{(const Slot *)src->table});
+        if constexpr (std::is_same<SINK, kh::JkStats<true>>::value) go(kh::PbNone{});
+        else with_probe(prb, go);
+    });
     HIP_TRY(on, hipGetLastError());
     return KH_OK;
 }
 
 // a source: pending pushes counted, the table as it is, its stream idle and its counters exact
 int join_enter_source(kh_ctx *err, kh_ctx *s) {
-    int rc = enter(s, true, true, false, true, true);
+    int rc = enter(s, ENTER_READ);
     if (rc == KH_OK) rc = sync_counters(s);
     if (rc != KH_OK && err != s) err->last_error = s->last_error;
     return rc;

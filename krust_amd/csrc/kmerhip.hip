@@ -75,36 +75,36 @@ void read_knobs(Knobs &k) {
 #endif
 }
 
-int enter(kh_ctx *c, bool flush_pending, bool need_table, bool keep_window, bool narrow_ok, bool reader) {
+int enter(kh_ctx *c, Entry how) {
     if (!c) return KH_ERR_BAD_ARG;
-    if (!reader) c->ts.on = false;  // (whatever may change the table, or takes the partition buffers, ends a text stream)
-    if (!reader) c->un.live = false;  // (... and makes the unitigs of kh_unitigs_begin stale: their copies refuse)
+    if (!how.reader) c->ts.on = false;  // (whatever may change the table, or takes the partition buffers, ends a text stream)
+    if (!how.reader) c->un.live = false;  // (... and makes the unitigs of kh_unitigs_begin stale: their copies refuse)
 #if KH_TESTING
     read_knobs(c->knobs);  // (tests flip the switches between calls on one context; the product library reads them once, at kh_create)
 #endif
     if (c->poisoned) return fail(c, KH_ERR_STATE, "context is poisoned by an earlier error");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->win_open && !keep_window) {
+    if (c->win_open && !how.keep_window) {
         int rc = close_fresh_window(c);
         if (rc != KH_OK) return rc;
     }
-    if (flush_pending && c->acc_len) {
+    if (how.flush_pending && c->acc_len) {
         int rc = flush_acc(c, false);
         if (rc != KH_OK) return rc;
     }
-    if (flush_pending && c->txt_unscanned.on) {  // (KH_FLAG_DEFER_TEXT_SCAN: the last text's scan -- and its verdict -- is still to come)
+    if (how.flush_pending && c->txt_unscanned.on) {  // (KH_FLAG_DEFER_TEXT_SCAN: the last text's scan -- and its verdict -- is still to come)
         int rc = scan_unscanned(c);
         if (rc != KH_OK) return rc;
     }
-    if (flush_pending && c->txt_acc_len) {
+    if (how.flush_pending && c->txt_acc_len) {
         int rc = flush_text(c);
         if (rc != KH_OK) return rc;
     }
-    if (c->narrow && !narrow_ok) {
+    if (c->narrow && !how.narrow_ok) {
         int rc = ensure_wide(c);
         if (rc != KH_OK) return rc;
     }
-    return (need_table && !c->narrow) ? clear_if_dirty(c) : KH_OK;
+    return (how.need_table && !c->narrow) ? clear_if_dirty(c) : KH_OK;
 }
 
 int alloc_table(kh_ctx *c, u64 cap, Slot **out) {
@@ -188,6 +188,51 @@ int end_borrow(kh_ctx *c) {
     c->borrow_off[0] = c->borrow_off[1] = 0;
     return KH_OK;
 }
+// ---- a call's scratch (ctx.hip.h, CallScratch) ----
+CallScratch::CallScratch(kh_ctx *ctx) : c(ctx), loan0(ctx->borrow_off[0]), loan1(ctx->borrow_off[1]) {}
+
+void *CallScratch::take(u64 bytes) {
+    const u64 need = (std::max<u64>(bytes, 16) + 4095) & ~4095ull;
+    if (!c->borrow_on) {  // the partition buffers are idle: every batch is counted (enter() flushed)
+        uint8_t *const base[2] = {c->keysA, c->keysB};
+        const u64 cap[2] = {c->key_cap, c->keyb_cap};
+        for (int i = 0; i < 2; ++i)
+            if (base[i] && used[i] + need <= cap[i]) {
+                void *p = base[i] + used[i];
+                used[i] += need;
+                return p;
+            }
+    } else if (void *p = borrow(c, need)) {
+        lent = true;
+        return p;
+    }
+    return fresh(need);
+}
+
+void *CallScratch::fresh(u64 bytes) {
+    void *p = nullptr;
+    if (dev_malloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    try {
+        owned.push_back(p);
+    } catch (...) {
+        (void)dev_free(p);
+        return nullptr;
+    }
+    return p;
+}
+
+CallScratch::~CallScratch() {
+    if (!owned.empty()) (void)hipStreamSynchronize(c->stream);
+    for (void *p : owned) (void)dev_free(p);
+    if (lent) {  // (a loan taken for this call alone goes back)
+        c->borrow_off[0] = loan0;
+        c->borrow_off[1] = loan1;
+    }
+}
+
 // an EMPTY table of another size: nothing to move, nothing to allocate yet
 void resize_empty_table(kh_ctx *c, u64 newcap) {
     drop_table(c);
@@ -623,7 +668,7 @@ extern "C" int kh_reset(kh_ctx *c) {
         c->poisoned = false;
         c->poisoned_by = KH_OK;
     }
-    int rc = enter(c, false, false, false, true);  // (touches no slot: the reset is lazy, and a table nobody has needed yet stays unallocated)
+    int rc = enter(c, ENTER_PUSH);  // (touches no slot: the reset is lazy, and a table nobody has needed yet stays unallocated)
     if (rc != KH_OK) return rc;
     if (c->cstream) HIP_TRY(c, hipStreamSynchronize(c->cstream));
     c->acc_len = c->acc_carry = 0;  // pushes not yet counted are forgotten with everything else
@@ -658,7 +703,7 @@ extern "C" int kh_reset(kh_ctx *c) {
 }
 
 extern "C" int kh_finish(kh_ctx *c, kh_stats *st) {
-    int rc = enter(c, true, true, false, true, true);
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     rc = sync_counters(c);
     if (rc != KH_OK) return rc;
@@ -709,7 +754,7 @@ int read_cursor(kh_ctx *c, u64 *cursor, u64 *big) {
 }  // namespace khi
 
 extern "C" int kh_result_size(kh_ctx *c, uint64_t min_count, uint64_t *n) {
-    int rc = enter(c, true, true, false, true, true);
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (!n) return fail(c, KH_ERR_BAD_ARG, "n is NULL");
     rc = zero_cursors(c);
@@ -750,74 +795,57 @@ int compact_pairs(kh_ctx *c, u64 *d_keys, u64 *d_counts, u64 cap, u64 min_count,
 
 extern "C" int kh_result_copy_device(kh_ctx *c, uint64_t *d_keys, uint64_t *d_counts, uint64_t cap,
                                      uint64_t min_count, uint64_t *n) {
-    int rc = enter(c, true, true, false, true);
+    int rc = enter(c, ENTER_READ_TAKE);
     if (rc != KH_OK) return rc;
     if (!n || (cap && (!d_keys || !d_counts))) return fail(c, KH_ERR_BAD_ARG, "NULL output");
     return compact_pairs(c, (u64 *)d_keys, (u64 *)d_counts, cap, min_count, (u64 *)n);
 }
 
-extern "C" int kh_result_copy(kh_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t cap, uint64_t min_count,
-                              uint64_t *n) {
-    int rc = enter(c, true, true, false, true);
+namespace khi {
+int result_enter(kh_ctx *c, const void *keys, const void *counts, u64 cap, u64 min_count, uint64_t *n, uint64_t *need) {
+    int rc = enter(c, ENTER_READ_TAKE);
     if (rc != KH_OK) return rc;
     if (!n || (cap && (!keys || !counts))) return fail(c, KH_ERR_BAD_ARG, "NULL output");
-    uint64_t need = 0;
-    rc = kh_result_size(c, min_count, &need);
-    if (rc != KH_OK) return rc;
-    if (need > cap) {
-        *n = 0;
-        return fail(c, KH_ERR_RANGE, "output arrays too small");
-    }
     *n = 0;
-    if (need == 0) return KH_OK;
+    if ((rc = kh_result_size(c, min_count, need)) != KH_OK) return rc;
+    if (*need > cap) return fail(c, KH_ERR_RANGE, "output arrays too small");
+    return KH_OK;
+}
+}  // namespace khi
+
+extern "C" int kh_result_copy(kh_ctx *c, uint64_t *keys, uint64_t *counts, uint64_t cap, uint64_t min_count,
+                              uint64_t *n) {
+    uint64_t need = 0;
+    int rc = result_enter(c, keys, counts, cap, min_count, n, &need);
+    if (rc != KH_OK || need == 0) return rc;
     // The compacted pairs need two device arrays on their way out.  The partition buffers are idle here (every batch is
     // counted: enter() flushed) and, after any sizeable count, far larger than the result: use them instead of two fresh
     // multi-gigabyte allocations (mapping and unmapping 17 GB cost more than the compaction itself).
-    // (Round 5: unless a merge has BORROWED parts of them -- its shard table may live there: then only what is not lent out,
-    //  through the same bump allocator, handed back below.)
-    uint64_t *dk = nullptr, *dc = nullptr;
-    const u64 loan0 = c->borrow_off[0], loan1 = c->borrow_off[1];
-    bool scratch = !c->borrow_on && c->keysA && c->keysB && c->key_cap >= need * sizeof(u64) && c->keyb_cap >= need * sizeof(u64);
-    if (scratch) {
-        dk = reinterpret_cast<uint64_t *>(c->keysA);
-        dc = reinterpret_cast<uint64_t *>(c->keysB);
-    } else if (c->borrow_on && (dk = (uint64_t *)borrow(c, need * sizeof(u64))) != nullptr && (dc = (uint64_t *)borrow(c, need * sizeof(u64))) != nullptr) {
-        scratch = true;
-    } else if ((c->borrow_off[0] = loan0, c->borrow_off[1] = loan1, dk = dc = nullptr, false) ||
-               dev_malloc((void **)&dk, need * sizeof(u64)) != hipSuccess || dev_malloc((void **)&dc, need * sizeof(u64)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (dk) (void)dev_free(dk);
-        return soft_oom(c, "hipMalloc(result)");
-    }
+    // (Round 5: unless a merge has BORROWED parts of them -- its shard table may live there: then only what is not lent out.)
+    CallScratch sc(c);
+    uint64_t *const dk = (uint64_t *)sc.take(need * sizeof(u64));
+    uint64_t *const dc = dk ? (uint64_t *)sc.take(need * sizeof(u64)) : nullptr;
+    if (!dc) return soft_oom(c, "hipMalloc(result)");
     uint64_t got = 0;
     rc = kh_result_copy_device(c, dk, dc, need, min_count, &got);
     if (rc == KH_OK) rc = d2h_staged(c, keys, dk, got * sizeof(u64));
     if (rc == KH_OK) rc = d2h_staged(c, counts, dc, got * sizeof(u64));
     if (rc == KH_OK) *n = got;
-    if (!scratch) {
-        (void)dev_free(dk);
-        (void)dev_free(dc);
-    }
-    c->borrow_off[0] = loan0;  // (a loan taken for this call alone goes back)
-    c->borrow_off[1] = loan1;
     return rc;
 }
 
 extern "C" int kh_histogram(kh_ctx *c, uint64_t min_count, uint64_t *count, uint64_t *freq, uint64_t cap,
                             uint64_t *n) {
-    int rc = enter(c, true, true, false, true, true);
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (!n || (cap && (!count || !freq))) return fail(c, KH_ERR_BAD_ARG, "NULL output");
-    u64 *d_dense = nullptr, *d_big = nullptr;
     u64 big_cap = 1ull << 16;
     std::vector<u64> dense(kh::HIST_DENSE), big;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        if (dev_malloc((void **)&d_dense, kh::HIST_DENSE * sizeof(u64)) != hipSuccess ||
-            dev_malloc((void **)&d_big, big_cap * sizeof(u64)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (d_dense) (void)dev_free(d_dense);
-            return soft_oom(c, "hipMalloc(histogram)");
-        }
+        CallScratch sc(c);  // (of this attempt: the first list goes back before the exactly sized one is allocated)
+        u64 *const d_dense = (u64 *)sc.fresh(kh::HIST_DENSE * sizeof(u64));
+        u64 *const d_big = d_dense ? (u64 *)sc.fresh(big_cap * sizeof(u64)) : nullptr;
+        if (!d_big) return soft_oom(c, "hipMalloc(histogram)");
         rc = zero_cursors(c);
         if (rc == KH_OK && hipMemsetAsync(d_dense, 0, kh::HIST_DENSE * sizeof(u64), c->stream) != hipSuccess)
             rc = fail(c, KH_ERR_HIP, "hipMemsetAsync(histogram)");
@@ -838,9 +866,6 @@ extern "C" int kh_histogram(kh_ctx *c, uint64_t min_count, uint64_t *count, uint
                 (nbig && hipMemcpy(big.data(), d_big, nbig * sizeof(u64), hipMemcpyDeviceToHost) != hipSuccess))
                 rc = fail(c, KH_ERR_HIP, "hipMemcpy(histogram)");
         }
-        (void)dev_free(d_dense);
-        (void)dev_free(d_big);
-        d_dense = d_big = nullptr;
         if (rc != KH_OK) return rc;
         if (nbig <= big_cap) break;
         big_cap = nbig;  // second pass with an exactly sized list
@@ -864,16 +889,14 @@ extern "C" int kh_histogram(kh_ctx *c, uint64_t min_count, uint64_t *count, uint
 }
 
 extern "C" int kh_lookup(kh_ctx *c, const uint64_t *keys, uint64_t n, uint64_t *counts) {
-    int rc = enter(c, true, true, false, true, true);
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (n == 0) return KH_OK;
     if (!keys || !counts) return fail(c, KH_ERR_BAD_ARG, "NULL argument");
-    u64 *dk = nullptr, *dc = nullptr;
-    if (dev_malloc((void **)&dk, n * sizeof(u64)) != hipSuccess || dev_malloc((void **)&dc, n * sizeof(u64)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (dk) (void)dev_free(dk);
-        return soft_oom(c, "hipMalloc(lookup)");
-    }
+    CallScratch sc(c);
+    u64 *const dk = (u64 *)sc.fresh(n * sizeof(u64));
+    u64 *const dc = dk ? (u64 *)sc.fresh(n * sizeof(u64)) : nullptr;
+    if (!dc) return soft_oom(c, "hipMalloc(lookup)");
     hipError_t e = hipMemcpyAsync(dk, keys, n * sizeof(u64), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         if (c->narrow)
@@ -886,8 +909,6 @@ extern "C" int kh_lookup(kh_ctx *c, const uint64_t *keys, uint64_t n, uint64_t *
     }
     if (e == hipSuccess) e = hipMemcpyAsync(counts, dc, n * sizeof(u64), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)dev_free(dk);
-    (void)dev_free(dc);
     if (e != hipSuccess) return fail(c, KH_ERR_HIP, "kh_lookup", e);
     return KH_OK;
 }

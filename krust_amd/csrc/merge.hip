@@ -19,11 +19,9 @@ extern "C" int kh_export_by_owner_device(kh_ctx *c, uint32_t nparts, uint64_t *d
     if (nparts < 1 || nparts > kh::MAX_PARTS || !part_counts) return fail(c, KH_ERR_BAD_ARG, "bad nparts/part_counts");
     rc = sync_counters(c);
     if (rc != KH_OK) return rc;
-    u64 *d_parts = nullptr;
-    if (dev_malloc((void **)&d_parts, nparts * sizeof(u64)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, KH_ERR_OOM, "hipMalloc(parts)");
-    }
+    CallScratch sc(c);
+    u64 *const d_parts = (u64 *)sc.fresh(nparts * sizeof(u64));
+    if (!d_parts) return fail(c, KH_ERR_OOM, "hipMalloc(parts)");
     std::vector<u64> h(nparts, 0);
     hipError_t e = hipMemsetAsync(d_parts, 0, nparts * sizeof(u64), c->stream);
     if (e == hipSuccess) {
@@ -40,15 +38,9 @@ extern "C" int kh_export_by_owner_device(kh_ctx *c, uint32_t nparts, uint64_t *d
         total += h[p];
         part_counts[p] = h[p];
     }
-    if (e == hipSuccess && total > cap) {
-        (void)dev_free(d_parts);
-        return fail(c, KH_ERR_RANGE, "export arrays too small");
-    }
+    if (e == hipSuccess && total > cap) return fail(c, KH_ERR_RANGE, "export arrays too small");
     if (e == hipSuccess && total) {
-        if (!d_keys || !d_counts) {
-            (void)dev_free(d_parts);
-            return fail(c, KH_ERR_BAD_ARG, "NULL output");
-        }
+        if (!d_keys || !d_counts) return fail(c, KH_ERR_BAD_ARG, "NULL output");
         e = hipMemcpyAsync(d_parts, offs.data(), nparts * sizeof(u64), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(kh::owner_scatter_kernel, dim3(grid_for(c->cap)), dim3(kh::BLOCK), 0, c->stream,
@@ -57,7 +49,6 @@ extern "C" int kh_export_by_owner_device(kh_ctx *c, uint32_t nparts, uint64_t *d
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
-    (void)dev_free(d_parts);
     if (e != hipSuccess) return fail(c, KH_ERR_HIP, "kh_export_by_owner_device", e);
     return KH_OK;
 }
@@ -89,18 +80,14 @@ extern "C" int kh_merge_pairs(kh_ctx *c, const uint64_t *keys, const uint64_t *c
     if (rc != KH_OK) return rc;
     if (n == 0) return KH_OK;
     if (!keys || !counts) return fail(c, KH_ERR_BAD_ARG, "NULL argument");
-    uint64_t *dk = nullptr, *dc = nullptr;
-    if (dev_malloc((void **)&dk, n * sizeof(u64)) != hipSuccess || dev_malloc((void **)&dc, n * sizeof(u64)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (dk) (void)dev_free(dk);
-        return fail(c, KH_ERR_OOM, "hipMalloc(merge)");
-    }
+    CallScratch sc(c);
+    uint64_t *const dk = (uint64_t *)sc.fresh(n * sizeof(u64));
+    uint64_t *const dc = dk ? (uint64_t *)sc.fresh(n * sizeof(u64)) : nullptr;
+    if (!dc) return fail(c, KH_ERR_OOM, "hipMalloc(merge)");
     hipError_t e = hipMemcpyAsync(dk, keys, n * sizeof(u64), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dc, counts, n * sizeof(u64), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) rc = kh_merge_pairs_device(c, dk, dc, n);
     hipError_t e2 = hipStreamSynchronize(c->stream);
-    (void)dev_free(dk);
-    (void)dev_free(dc);
     if (e != hipSuccess || e2 != hipSuccess) return fail(c, KH_ERR_HIP, "kh_merge_pairs", e != hipSuccess ? e : e2);
     return rc;
 }
@@ -142,7 +129,9 @@ extern "C" int kh_merge_dense_device(kh_ctx *c, const uint64_t *d_dense, uint64_
 
 // ---- hash-range sharding: region-ordered export and LDS merge ------------------------------------
 extern "C" int kh_set_shard(kh_ctx *c, uint32_t index, uint32_t count) {
-    int rc = enter(c, true, false);  // touches no slot: a lazily reset table stays lazily reset
+    Entry how = ENTER_WRITE;
+    how.need_table = false;  // touches no slot: a lazily reset table stays lazily reset
+    int rc = enter(c, how);
     if (rc != KH_OK) return rc;
     if (count == 0 || (count & (count - 1)) || index >= count || count > (uint32_t)kh::MAX_SENDERS)
         return fail(c, KH_ERR_BAD_ARG, "shard count must be a power of two (<= 64) and index < count");
@@ -212,7 +201,9 @@ int recount_touched_heads(kh_ctx *c, u64 nregions) {
 int export_regions(kh_ctx *c, int fmt, uint32_t nparts, void *d_keys, uint64_t *d_counts, uint64_t cap,
                    uint32_t *d_region_counts, uint64_t region_cap, uint64_t *part_counts, uint64_t *table_regions, u64 *d_digest, bool *digest_done) {
     if (digest_done) *digest_done = false;
-    int rc = enter(c, true, true, false, fmt != XF_WIDE);  // (packed and heads come straight out of the 8-byte image)
+    Entry how = ENTER_WRITE;
+    how.narrow_ok = fmt != XF_WIDE;  // (packed and heads come straight out of the 8-byte image)
+    int rc = enter(c, how);
     if (rc != KH_OK) return rc;
     const bool packed = fmt != XF_WIDE;
     const u64 nregions = c->cap / kh::REGION_SLOTS;
@@ -338,7 +329,7 @@ int export_regions(kh_ctx *c, int fmt, uint32_t nparts, void *d_keys, uint64_t *
 // the window) -- what a pipelined exchange needs to announce the sizes of ALL its pieces up front.
 extern "C" int kh_region_unit_counts_device(kh_ctx *c, uint32_t unit_bytes, uint32_t *d_region_counts, uint64_t region_cap,
                                             uint64_t *table_regions) {
-    int rc = enter(c, true, true, false, true);
+    int rc = enter(c, ENTER_READ_TAKE);
     if (rc != KH_OK) return rc;
     if (unit_bytes != 4 && unit_bytes != 8 && unit_bytes != 16) return fail(c, KH_ERR_BAD_ARG, "unit_bytes is 4 (heads), 8 (packed) or 16 (pairs)");
     const u64 nregions = c->cap / kh::REGION_SLOTS;
@@ -416,8 +407,10 @@ int merge_regions(kh_ctx *c, int fmt, uint32_t nsenders, uint64_t sender_regions
     // a FRESH merge rewrites every region of a lazily reset table; in pieces (kh_set_region_window), the
     // pieces still to come stay unwritten until then (win_open)
     const bool windowed = c && c->win_n > 1;
-    // (narrow_ok: a fresh merge of packed pairs / heads builds the shard as the 8-byte image, piece by piece -- decided below)
-    int rc = enter(c, true, false, windowed && c->win_open && c->win_open_n == c->win_n && !(c->win_mask & (1ull << c->win_piece)), true);
+    // (the image stays: a fresh merge of packed pairs / heads builds the shard as the 8-byte image, piece by piece -- decided below)
+    Entry how = ENTER_PUSH_DEVICE;
+    how.keep_window = windowed && c->win_open && c->win_open_n == c->win_n && !(c->win_mask & (1ull << c->win_piece));
+    int rc = enter(c, how);
     if (rc != KH_OK) return rc;
     const bool packed = fmt != XF_WIDE;
     if (nsenders < 1 || nsenders > (uint32_t)kh::MAX_SENDERS || !d_keys || (!packed && !d_counts) || !d_region_counts)

@@ -169,3 +169,20 @@ struct JsNarrow {
 };
 
 }  // namespace kh
+
+// ---- host side: the one place that says which form a context's table is in ------------------------------------------------------
+namespace khi {
+
+// f(view): the probe of c's table / its slots as a source, in the form the table is in -- f is instantiated with both views
+template <typename F>
+void with_probe(const kh_ctx *c, F f) {
+    if (c->narrow) f(kh::PfNarrow{(const u64 *)c->ntab, c->narrow_g});
+    else f(kh::PfWide{table_geom(c, c->table, c->cap)});
+}
+template <typename F>
+void with_source(const kh_ctx *c, F f) {
+    if (c->narrow) f(kh::JsNarrow{(const u64 *)c->ntab, c->narrow_g});
+    else f(kh::JsWide{(const Slot *)c->table});
+}
+
+}  // namespace khi

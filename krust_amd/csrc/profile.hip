@@ -406,7 +406,7 @@ int profile_range(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 
     u64 blocks = ntiles < (u64)grid_cap() ? ntiles : (u64)grid_cap();
     const uint32_t tpb = (uint32_t)((ntiles + blocks - 1) / blocks);  // contiguous tiles per workgroup: the look-back is carried in LDS
     blocks = (ntiles + tpb - 1) / tpb;
-    auto launch = [&](auto tab) {
+    with_probe(c, [&](auto tab) {
         typedef decltype(tab) TAB;
         if (rec && use_qual)
             hipLaunchKernelGGL((kh::profile_records_kernel<true, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase, qbase, qaligned,
@@ -422,9 +422,7 @@ int profile_range(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 
         else
             hipLaunchKernelGGL((kh::profile_kernel<false, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase,
                                (const uint8_t *)nullptr, 0, vbeg, vend, ntiles, tpb, c->k, 0u, tab, d_out, nout);
-    };
-    if (c->narrow) launch(kh::PfNarrow{(const u64 *)c->ntab, c->narrow_g});
-    else launch(kh::PfWide{table_geom(c, c->table, c->cap)});
+    });
     HIP_TRY(c, hipGetLastError());
     return KH_OK;
 }
@@ -499,7 +497,7 @@ extern "C" int kh_profile_device(kh_ctx *c, const uint8_t *d_bases, const uint8_
     if (!c) return KH_ERR_BAD_ARG;
     if (n && (!d_bases || !d_out)) return fail(c, KH_ERR_BAD_ARG, "kh_profile_device: NULL argument");
     if ((uintptr_t)d_out & 3) return fail(c, KH_ERR_BAD_ARG, "kh_profile_device: d_out is not 4-byte aligned");
-    int rc = enter(c, true, true, false, true, true);
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (n == 0) return KH_OK;
     rc = profile_range(c, d_bases, d_qual, n, n, d_out);
@@ -512,7 +510,7 @@ extern "C" int kh_profile(kh_ctx *c, const uint8_t *bases, const uint8_t *qual, 
     if (!c) return KH_ERR_BAD_ARG;
     if (n && (!bases || !out)) return fail(c, KH_ERR_BAD_ARG, "kh_profile: NULL argument");
     if ((uintptr_t)out & 3) return fail(c, KH_ERR_BAD_ARG, "kh_profile: out is not 4-byte aligned");
-    int rc = enter(c, true, true, false, true, true);
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (n == 0) return KH_OK;
     const bool with_qual = qual != nullptr && c->minq >= 0;
@@ -567,7 +565,7 @@ extern "C" int kh_profile_records_device(kh_ctx *c, const uint8_t *d_bases, cons
     if ((n && !d_bases) || (nrec && (!d_rec_start || !d_rows))) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records_device: NULL argument");
     if ((uintptr_t)d_rows & 3) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records_device: d_rows is not 4-byte aligned");
     if ((uintptr_t)d_rec_start & 7) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records_device: d_rec_start is not 8-byte aligned");
-    int rc = enter(c, true, true, false, true, true);
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (nrec == 0) return KH_OK;
     const int sumw = pr_sum_word(d_rows);
@@ -592,7 +590,7 @@ extern "C" int kh_profile_records(kh_ctx *c, const uint8_t *bases, const uint8_t
         if (rec_start[r + 1] - rec_start[r] > 0xFFFFFFFFull) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records: a record of 2^32 or more window starts");
     }
     if (nrec && rec_start[nrec] > n) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records: rec_start[nrec] is beyond n");
-    int rc = enter(c, true, true, false, true, true);
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (nrec == 0) return KH_OK;
     if ((rc = records_buffers(c, nrec)) != KH_OK) return rc;

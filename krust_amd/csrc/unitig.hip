@@ -610,7 +610,7 @@ struct ClipJob {
 // One round of tip clipping behind the links of c, while unitigs_build's scratch is live: the two decision kernels on c's stream,
 // then the surviving nodes into job->dst on ITS stream, in ranges it has room for (as combine_scan of join.hip).  Every failure
 // before the first insert leaves dst as it was.
-int clip_step(kh_ctx *c, ClipJob *job, SortScratch &sc, u64 n, u64 nu, u64 nl, const u64 *keys, const u64 *counts, const uint32_t *order,
+int clip_step(kh_ctx *c, ClipJob *job, CallScratch &sc, u64 n, u64 nu, u64 nl, const u64 *keys, const u64 *counts, const uint32_t *order,
               const uint32_t *ordu, const u64 *loff, uint32_t *d_err) {
     kh_ctx *const dst = job->dst;
     uint8_t *const cand = (uint8_t *)sc.take(nu);
@@ -653,7 +653,7 @@ int clip_step(kh_ctx *c, ClipJob *job, SortScratch &sc, u64 n, u64 nu, u64 nl, c
 
 // linked: kh_unitigs_begin_linked -- the link array behind the same kernels; nothing of it is launched or allocated without.
 // clip: kh_clip_tips_into -- linked, without the base array, and clip_step() behind the links.
-int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJob *clip = nullptr) {
+int unitigs_build(kh_ctx *c, u64 n, u64 mc, CallScratch &sc, bool linked, ClipJob *clip = nullptr) {
     const uint32_t n32 = (uint32_t)n, k = c->k;
     const u64 states = 2 * n;
     u64 *const keys = (u64 *)sc.take(n * sizeof(u64));
@@ -674,19 +674,13 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJo
     HIP_TRY(c, hipMemsetAsync(slot2id, 0xFF, c->cap * sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(circ, 0, n, c->stream));
     HIP_TRY(c, hipMemsetAsync(d_flag, 0, 2 * sizeof(uint32_t), c->stream));
-    if (c->narrow) {
-        const kh::PfNarrow prb{(const u64 *)c->ntab, c->narrow_g};
-        hipLaunchKernelGGL((kh::unitig_index_kernel<kh::PfNarrow>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, mc, prb,
+    with_probe(c, [&](auto prb) {
+        typedef decltype(prb) PRB;
+        hipLaunchKernelGGL((kh::unitig_index_kernel<PRB>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, mc, prb,
                            c->cap, slot2id, masks);
-        hipLaunchKernelGGL((kh::unitig_link_kernel<kh::PfNarrow>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, prb,
+        hipLaunchKernelGGL((kh::unitig_link_kernel<PRB>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, prb,
                            c->cap, (const uint32_t *)slot2id, (const uint8_t *)masks, next);
-    } else {
-        const kh::PfWide prb{table_geom(c, c->table, c->cap)};
-        hipLaunchKernelGGL((kh::unitig_index_kernel<kh::PfWide>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, mc, prb,
-                           c->cap, slot2id, masks);
-        hipLaunchKernelGGL((kh::unitig_link_kernel<kh::PfWide>), dim3(uni_grid(n)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k, prb,
-                           c->cap, (const uint32_t *)slot2id, (const uint8_t *)masks, next);
-    }
+    });
     HIP_TRY(c, hipGetLastError());
 
     bool open = false;
@@ -762,17 +756,11 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJo
             c->un.links = nullptr;
             return soft_oom(c, "hipMalloc(unitig links)");
         }
-        if (c->narrow) {
-            const kh::PfNarrow prb{(const u64 *)c->ntab, c->narrow_g};
-            hipLaunchKernelGGL((kh::unitig_link_out_kernel<kh::PfNarrow>), dim3(uni_grid(2 * nu)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k,
+        with_probe(c, [&](auto prb) {
+            hipLaunchKernelGGL((kh::unitig_link_out_kernel<decltype(prb)>), dim3(uni_grid(2 * nu)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k,
                                prb, c->cap, nu, (const u64 *)c->un.rows, (const uint32_t *)order, (const uint32_t *)slot2id, (const uint8_t *)masks,
                                (const uint32_t *)head, (const uint32_t *)posg, (const u64 *)uidx, (const u64 *)loff, nl, c->un.links, d_flag + 1);
-        } else {
-            const kh::PfWide prb{table_geom(c, c->table, c->cap)};
-            hipLaunchKernelGGL((kh::unitig_link_out_kernel<kh::PfWide>), dim3(uni_grid(2 * nu)), dim3(kh::BLOCK), 0, c->stream, (const u64 *)keys, n32, k,
-                               prb, c->cap, nu, (const u64 *)c->un.rows, (const uint32_t *)order, (const uint32_t *)slot2id, (const uint8_t *)masks,
-                               (const uint32_t *)head, (const uint32_t *)posg, (const u64 *)uidx, (const u64 *)loff, nl, c->un.links, d_flag + 1);
-        }
+        });
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(&bad, d_flag + 1, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -788,7 +776,7 @@ int unitigs_build(kh_ctx *c, u64 n, u64 mc, SortScratch &sc, bool linked, ClipJo
 // What the two copies check before they write anything.
 int unitigs_copy_enter(kh_ctx *c, const char *who, const void *rows, u64 row_cap, const void *bases, u64 base_cap) {
     if (!c) return KH_ERR_BAD_ARG;
-    int rc = enter(c, true, true, false, true, true);  // a reader
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (!c->un.live)
         return fail(c, KH_ERR_STATE, (std::string(who) + ": no unitigs: kh_unitigs_begin first (anything that changes the table makes them stale)").c_str());
@@ -812,7 +800,7 @@ int unitigs_begin(kh_ctx *c, const char *who, uint64_t min_count, uint64_t *n_un
     if (linked) *n_links = 0;
     if (c->shard_shift)
         return fail(c, KH_ERR_STATE, (std::string(who) + ": the table is a shard; its k-mers' neighbours live on other owners").c_str());
-    int rc = enter(c, true, true, false, true);  // as kh_result_sorted_device: the partition buffers are taken, a text stream ends
+    int rc = enter(c, ENTER_READ_TAKE);
     if (rc != KH_OK) return rc;
     unitigs_release(c);
     const u64 mc = min_count ? min_count : 1;
@@ -821,7 +809,7 @@ int unitigs_begin(kh_ctx *c, const char *who, uint64_t min_count, uint64_t *n_un
     if (n > 0x7FFFFFFFull) return fail(c, KH_ERR_RANGE, (std::string(who) + ": more than 2^31 - 1 nodes: node ids are 32-bit").c_str());
     if (n) {
         {
-            SortScratch sc(c);
+            CallScratch sc(c);
             rc = unitigs_build(c, n, mc, sc, linked);
             if (rc != KH_OK) (void)hipStreamSynchronize(c->stream);  // (before the scratch goes back)
         }
@@ -841,7 +829,7 @@ int unitigs_begin(kh_ctx *c, const char *who, uint64_t min_count, uint64_t *n_un
 // What the two link copies check before they write anything.
 int links_copy_enter(kh_ctx *c, const char *who, const void *links, u64 cap) {
     if (!c) return KH_ERR_BAD_ARG;
-    int rc = enter(c, true, true, false, true, true);  // a reader
+    int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (!c->un.live)
         return fail(c, KH_ERR_STATE,
@@ -876,9 +864,9 @@ extern "C" int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, u
         if (r != KH_OK) dst->last_error = src->last_error;
         return r;
     };
-    if ((rc = enter(src, true, true, false, true)) != KH_OK) return from_src(rc);  // as kh_unitigs_begin_linked
+    if ((rc = enter(src, ENTER_READ_TAKE)) != KH_OK) return from_src(rc);
     unitigs_release(src);
-    if ((rc = enter(dst)) != KH_OK) return rc;  // as kh_combine_into
+    if ((rc = enter(dst)) != KH_OK) return rc;
     const u64 mc = min_count ? min_count : 1;
     uint64_t n = 0;
     if ((rc = kh_result_size(src, mc, &n)) != KH_OK) return from_src(rc);
@@ -886,7 +874,7 @@ extern "C" int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, u
     ClipJob job{dst, max_kmers, {0, 0, 0, 0, 0, 0, 0, 0}, false};
     if (n) {
         {
-            SortScratch sc(src);
+            CallScratch sc(src);
             rc = unitigs_build(src, n, mc, sc, true, &job);
             if (rc != KH_OK) {
                 (void)hipStreamSynchronize(src->stream);  // (before the scratch goes back)

@@ -777,6 +777,46 @@ def test_writing_calls(tr, name, lo, hi, mode):
     sweep(tr, cases[name], mode, lo, hi)
 
 
+# ---- kh_export_by_owner_device: a writing call whose result lands in the caller's arrays --------------------------------------------
+NPARTS = 4
+
+
+class ExportByOwner(Writer):
+    """The reads counted (prep), then the pairs exported by owner into device arrays of the caller.  The call's own scratch is the
+    per-owner cursors; from state (b) it also widens the 8-byte image.  The clean run: every part holds exactly its own keys, all
+    parts together the oracle's pairs, and the table is what it was."""
+
+    def __init__(self, name, make):
+        Writer.__init__(self, name, make, self.export_steps, prep=1)
+
+    def export_steps(self, dc, I, st):
+        import torch
+        tb, _ = I.device()
+        n = I.keys.size
+        if "xk" not in st:
+            st["xk"], st["xc"] = (torch.zeros(n, dtype=torch.int64, device="cuda") for _ in range(2))
+            st["parts"] = np.zeros(NPARTS, dtype=U64)
+            torch.cuda.synchronize()
+        return [lambda: lib().kh_push_device(h(dc), tb.data_ptr(), None, tb.numel()),
+                lambda: lib().kh_export_by_owner_device(h(dc), NPARTS, st["xk"].data_ptr(), st["xc"].data_ptr(), n, st["parts"].ctypes.data)]
+
+    def ok(self, st):
+        I = st["I"]
+        keys, counts, parts = st["xk"].cpu().numpy().view(U64), st["xc"].cpu().numpy().view(U64), st["parts"]
+        assert int(parts.sum()) == I.keys.size
+        owners = np.array([native.owner(int(x), I.k, NPARTS) for x in keys])
+        assert np.array_equal(owners, np.repeat(np.arange(NPARTS), parts.astype(np.int64)))   # grouped by owner, in owner order
+        order = np.argsort(keys, kind="stable")
+        assert np.array_equal(keys[order], I.keys) and np.array_equal(counts[order], I.counts)
+        table_is(st["dcs"][0], I)
+
+
+@pytest.mark.parametrize("mode", ["", "+"], ids=["n", "n+"])
+@pytest.mark.parametrize("state", ["a", "b-widens"])
+def test_export_by_owner(tr, state, mode):
+    sweep(tr, ExportByOwner("export_by_owner-%s" % state, mk_direct if state == "a" else mk_part), mode)
+
+
 # ---- kh_create ---------------------------------------------------------------------------------------------------------------------------
 class Create(Op):
     name = "kh_create"
