@@ -131,6 +131,10 @@ pub mod sys {
         /// one round of tip clipping of `src`'s compacted graph at `min_count`: the k-mers of the surviving unitigs are added to `dst`
         /// (`count[key] += c`); `out` takes the 8 words KH_CLIP_* of the header names
         pub fn kh_clip_tips_into(dst: *mut KhCtx, src: *mut KhCtx, min_count: u64, max_kmers: u64, out: *mut u64) -> c_int;
+        /// one round of bubble popping of `src`'s compacted graph at `min_count`: of the parallel short unitigs between the same two
+        /// places only the best stays, the k-mers of the surviving unitigs are added to `dst` (`count[key] += c`); `out` takes the 9
+        /// words KH_POP_* of the header names
+        pub fn kh_pop_bubbles_into(dst: *mut KhCtx, src: *mut KhCtx, min_count: u64, max_kmers: u64, out: *mut u64) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
         pub fn kh_result_sorted(ctx: *mut KhCtx, keys: *mut u64, counts: *mut u64, cap: u64,
                                 min_count: u64, n: *mut u64) -> c_int;
@@ -244,6 +248,19 @@ pub const CLIP_CLIPPED_COUNT: usize = 4;
 pub const CLIP_KEPT_KMERS: usize = 5;
 pub const CLIP_KEPT_COUNT: usize = 6;
 pub const CLIP_LINKS: usize = 7;
+
+/// `KH_POP_WORDS`: the words of [`HipKmerMap::pop_bubbles_into`] -- unitigs, candidates, popped, popped_kmers, popped_count,
+/// kept_kmers, kept_count, links, bubbles (`POP_UNITIGS` .. `POP_BUBBLES`); the first eight mean what the `CLIP_*` words mean.
+pub const POP_WORDS: usize = 9;
+pub const POP_UNITIGS: usize = 0;
+pub const POP_CANDIDATES: usize = 1;
+pub const POP_POPPED: usize = 2;
+pub const POP_POPPED_KMERS: usize = 3;
+pub const POP_POPPED_COUNT: usize = 4;
+pub const POP_KEPT_KMERS: usize = 5;
+pub const POP_KEPT_COUNT: usize = 6;
+pub const POP_LINKS: usize = 7;
+pub const POP_BUBBLES: usize = 8;
 
 /// KH_SET_*: the set operation of `kh_combine_into`.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -558,6 +575,19 @@ impl HipKmerMap {
     pub fn clip_tips_into(&mut self, src: &HipKmerMap, min_count: u64, max_kmers: u64) -> Result<[u64; CLIP_WORDS], HipError> {
         let mut out = [0u64; CLIP_WORDS];
         check(self.ctx, unsafe { sys::kh_clip_tips_into(self.ctx, src.ctx, min_count, max_kmers, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// One round of bubble popping (`kh_pop_bubbles_into`): the unitigs and links of `src` at `min_count` are built on the device;
+    /// non-circular unitigs of at most `max_kmers` k-mers (a SNP branch has k; 2 k is a usual bound) with exactly one link out of
+    /// each end are parallel when their ends enter the same unordered pair of states, and of every such class only the one with
+    /// the greatest mean count stays (compared exactly, then the most k-mers, then the smallest index).  The k-mers of every
+    /// surviving unitig are added to THIS table with their counts from `src` (`count[key] += c`).  `src` is only read; unitigs it
+    /// had begun are released.  The borrow rules keep this table from being `src`.  Returns the nine words ([`POP_UNITIGS`] ..
+    /// [`POP_BUBBLES`]).
+    pub fn pop_bubbles_into(&mut self, src: &HipKmerMap, min_count: u64, max_kmers: u64) -> Result<[u64; POP_WORDS], HipError> {
+        let mut out = [0u64; POP_WORDS];
+        check(self.ctx, unsafe { sys::kh_pop_bubbles_into(self.ctx, src.ctx, min_count, max_kmers, out.as_mut_ptr()) })?;
         Ok(out)
     }
 

@@ -69,15 +69,15 @@ typedef enum kh_status {
 /* Allocation failures: what KH_ERR_OOM leaves behind.  One rule per kind of call; the comments further down only add to it.
  *   - A READING call takes the table as it is and allocates only for itself: kh_result_size / _copy / _copy_device / _sorted*,
  *     kh_result_text_*, kh_histogram, kh_lookup, kh_profile*, kh_profile_records*, kh_compare, kh_graph_*, kh_unitigs_* and the
- *     src side of kh_clip_tips_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
+ *     src side of kh_clip_tips_into / kh_pop_bubbles_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
  *     allocation, the table is unchanged and the context is NOT poisoned: the same call can be made again.  What the call
  *     allocated is released, except the scratch the context keeps for the next such call where that had been allocated
  *     before the failure: the pinned staging chunks and the copy stream of the host forms, the scan scratch (not after the
- *     sorted results, kh_unitigs_begin* and kh_clip_tips_into: there nothing stays), the tile arrays of a text stream, the
+ *     sorted results, kh_unitigs_begin*, kh_clip_tips_into and kh_pop_bubbles_into: there nothing stays), the tile arrays of a text stream, the
  *     chunk and row buffers of kh_profile / kh_profile_records, the words of kh_compare and kh_graph_stats.  kh_destroy
  *     releases them.  (Pushes that were still pending when the reading call came are counted first, as a writing call.)
  *   - A WRITING call changes the table: the pushes and the counting they trigger (also when a later call counts them), growth,
- *     the widening of the 8-byte image, kh_merge_*, and the dst of kh_combine_into / kh_clip_tips_into.  When one of its
+ *     the widening of the 8-byte image, kh_merge_*, and the dst of kh_combine_into / kh_clip_tips_into / kh_pop_bubbles_into.  When one of its
  *     allocations fails it returns KH_ERR_OOM, the table's content is unspecified and the context is POISONED: every later
  *     call except kh_reset, kh_destroy and kh_last_error returns KH_ERR_STATE.  A failure that the call can work round is
  *     no failure: a smaller text buffer, the 16-byte table instead of its 8-byte image, the partition buffers given back for
@@ -539,6 +539,53 @@ int kh_unitigs_links_copy(kh_ctx *ctx, uint64_t *links, uint64_t cap);
 #define KH_CLIP_KEPT_COUNT 6      /* sum of their counts, modulo 2^64 */
 #define KH_CLIP_LINKS 7           /* links of src's compacted graph */
 int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out /* KH_CLIP_WORDS, host */);
+
+/* ---- bubble popping: one round of removing short parallel branches (what assemblers do next to tip clipping) --- */
+/* Sequencing errors and heterozygous sites in the middle of a read leave bubbles: two or three short unitigs between the same
+ * two places.  Take the unitigs and links of kh_unitigs_begin_linked(src, min_count): rows, end states (i, +) and (i, -) and link
+ * words exactly as defined above.  out(i, s) is the set of links whose from-state is (i, s); to(w) is the low 32 bits of a link
+ * word, the entered state 2 * unitig + sign.
+ * CANDIDATE: unitig i is a candidate when it is not KH_UNI_CIRCULAR, KMERS <= max_kmers, out(i, +) and out(i, -) hold exactly
+ *   one link each, and neither link goes to unitig i itself (with either sign).
+ * EXITS(i): the unordered pair {to(out(i, +)), to(out(i, -))}; the two may be equal.
+ * PARALLEL: candidates i != b are parallel when EXITS(i) == EXITS(b).  The reported reading of a unitig is chosen by its end
+ *   keys, so two branches of one bubble are often reported in opposite directions: hence the unordered pair.  A palindromic
+ *   unitig is always entered as +, so the words compare as stored.  Being parallel is an equivalence relation among candidates;
+ *   all members of a class enter the same state, so a class has at most four members.
+ * BEATS: b beats i when COUNT_SUM_b * KMERS_i > COUNT_SUM_i * KMERS_b -- the greater mean count, compared EXACTLY as 128-bit
+ *   products, COUNT_SUM being the row's word as stored, modulo 2^64; no floating point --, or the products are equal and
+ *   KMERS_b > KMERS_i, or both are equal and b < i.
+ * POPPED: a candidate is popped when some parallel candidate beats it.  Exactly one member of every class survives; a candidate
+ *   with no parallel survives; every unitig that is no candidate survives -- a branch longer than max_kmers beside a short one
+ *   too, and the short one with it.
+ * One call is one round: it decides from the graph as built, nothing cascades inside it.  Popping never disconnects the two
+ *   places a class joins.  The unitigs that enter the state i's + end enters are found as for the rivals of tip clipping, by the
+ *   links out of that state reversed; i is always among them (the device tests it all the same; a failure, or link offsets that
+ *   do not add up, is KH_ERR_STATE "internal error").
+ * RESULT: every k-mer of every surviving unitig is added to dst with its count from src -- count += c, exactly as
+ *   kh_merge_pairs_device does: a fresh or kh_reset dst ends up holding S minus the popped k-mers.  K-mers of src below
+ *   min_count are not in S and are not copied.  max_kmers == 0 makes nothing a candidate: dst receives S.  Alternating this call
+ *   and kh_clip_tips_into between two contexts (kh_reset in between) simplifies the graph round by round; every reader of a
+ *   table then works on the simplified graph.
+ * ENTRY and ERRORS are those of kh_clip_tips_into, word for word: src is entered as kh_unitigs_begin_linked enters it (pending
+ *   pushes are counted first, the table is read in the form it is in, a text stream in progress ends, the partition buffers serve
+ *   as scratch, a shard is KH_ERR_STATE, more than 2^31 - 1 nodes is KH_ERR_RANGE); its table, counts and kh_stats are unchanged.
+ *   Any unitigs src had begun are RELEASED.  dst is entered as kh_combine_into enters its target.  dst == src, a NULL src or a
+ *   NULL out is KH_ERR_BAD_ARG; different k or different devices are KH_ERR_BAD_ARG, different shard states KH_ERR_STATE; every
+ *   such refusal leaves both contexts usable.  No memory for the call's scratch is KH_ERR_OOM with src usable and dst holding
+ *   what it held.  An empty S is KH_OK with all words 0.  The error text is on dst.
+ * Words 0 to 7 mean what the KH_CLIP_* words of the same index mean. */
+#define KH_POP_WORDS 9
+#define KH_POP_UNITIGS 0          /* unitigs of src at min_count */
+#define KH_POP_CANDIDATES 1
+#define KH_POP_POPPED 2           /* unitigs popped */
+#define KH_POP_POPPED_KMERS 3     /* sum of their KMERS */
+#define KH_POP_POPPED_COUNT 4     /* sum of their COUNT_SUM, modulo 2^64 */
+#define KH_POP_KEPT_KMERS 5       /* pairs added to dst */
+#define KH_POP_KEPT_COUNT 6       /* sum of their counts, modulo 2^64 */
+#define KH_POP_LINKS 7            /* links of src's compacted graph */
+#define KH_POP_BUBBLES 8          /* classes of at least two parallel candidates = survivors that beat someone */
+int kh_pop_bubbles_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out /* KH_POP_WORDS, host */);
 
 /* ---- multi-GPU merge (no reference counterpart) ----------- */
 /* Owner shard of a packed canonical k-mer among nparts shards: a fast-range of the top bits of

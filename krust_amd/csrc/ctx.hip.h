@@ -461,13 +461,13 @@ struct Entry {
     bool narrow_ok = false;     // the 8-byte image stays what it is (false: widened into the 16-byte table first)
     bool reader = false;        // the call only reads the table: a text stream in progress and the unitigs of kh_unitigs_begin survive it
 };
-// The pair and dense merges, the exports by owner, kh_comm_init, the dst of kh_combine_into / kh_clip_tips_into: a cleared
+// The pair and dense merges, the exports by owner, kh_comm_init, the dst of kh_combine_into / kh_clip_tips_into / kh_pop_bubbles_into: a cleared
 // 16-byte table, everything pending counted, whatever hangs on the table's content (text stream, unitigs, merge window) ended.
 constexpr Entry ENTER_WRITE{};
 // kh_finish, kh_result_size, kh_histogram, kh_lookup, kh_profile*, the sources of kh_compare / kh_combine_into, kh_graph_*,
 // the copies of the unitigs, kh_result_text_begin: everything pending counted, the table in the form it is in, nothing ended.
 constexpr Entry ENTER_READ{true, true, false, true, true};
-// kh_result_copy*, kh_result_sorted*, kh_region_unit_counts_device, kh_unitigs_begin*, the src of kh_clip_tips_into,
+// kh_result_copy*, kh_result_sorted*, kh_region_unit_counts_device, kh_unitigs_begin*, the src of kh_clip_tips_into / kh_pop_bubbles_into,
 // kh_merge_across: reads the table in the form it is in, but may take the idle partition buffers -- a text stream, whose chunks
 // live there, ends (and with it the unitigs).
 constexpr Entry ENTER_READ_TAKE{true, true, false, true, false};

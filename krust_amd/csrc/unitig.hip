@@ -32,6 +32,10 @@
 //   clip_decide_kernel         per candidate: its links, the links out of each entered state reversed (the rivals), their bytes and
 //                              rows -> one clipped byte; six of the eight words by wave reductions
 //   clip_keep_kernel           per node in unitig order: a node of a surviving unitig is upserted into the OTHER context's table
+// kh_pop_bubbles_into only, in the same place (one round of bubble popping, include/kmerhip.h); the keep kernel is clip's:
+//   pop_exits_kernel           per unitig: its row, the offsets of its two end states and its two links -> one exit word
+//   pop_decide_kernel          per candidate: the links out of its + exit reversed (the unitigs that enter the same place), their exit
+//                              words, the rows of the parallel ones (kh_pop_beats) -> one popped byte; seven of the nine words
 // No kernel waits for another workgroup, and no device loop is without a bound.  Rates were not measured (profiles/README.md r13).
 #include "ctx.hip.h"
 #include "probe.hip.h"
@@ -560,6 +564,115 @@ KH_GLOBAL __launch_bounds__(BLOCK) void clip_keep_kernel(TableGeom tg, u64 q0, u
     }
 }
 
+// ---- bubble popping (kh_pop_bubbles_into) -------------------------------------------------------------------------------------
+static_assert(KH_POP_KEPT_KMERS == KH_CLIP_KEPT_KMERS && KH_POP_KEPT_COUNT == KH_CLIP_KEPT_COUNT && KH_POP_WORDS >= KH_CLIP_WORDS,
+              "clip_keep_kernel writes the kept words of both rules");
+#define KH_POP_NO_EXITS (~0ull)  // no candidate (a to-state is below 2^32 - 2: no pair of them gives this word)
+
+// Per unitig: the unordered pair of the states its two ends enter, min << 32 | max, where it is a candidate (the rule:
+// include/kmerhip.h), else KH_POP_NO_EXITS.  No probes.
+// kernel-resource-usage (gfx950, hipcc -O3): 22 VGPRs, 44 SGPRs, no LDS, no scratch, no spills, 8 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void pop_exits_kernel(u64 nu, u64 nl, u64 max_kmers, const u64 *__restrict__ rows, const u64 *__restrict__ loff,
+                                                          const u64 *__restrict__ links, u64 *__restrict__ exits, uint32_t *__restrict__ err) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < nu; i += (u64)gridDim.x * BLOCK) {
+        const u64 kmers = rows[KH_UNI_WORDS * i + KH_UNI_KMERS], flags = rows[KH_UNI_WORDS * i + KH_UNI_FLAGS];
+        const u64 o0 = loff[2 * i], o1 = loff[2 * i + 1], o2 = loff[2 * i + 2];
+        u64 e = KH_POP_NO_EXITS;
+        if (o0 > o1 || o1 > o2 || o2 > nl || o1 - o0 > 4 || o2 - o1 > 4) {
+            *err = 1u;
+        } else if (!(flags & KH_UNI_CIRCULAR) && kmers <= max_kmers && o1 - o0 == 1 && o2 - o1 == 1) {
+            const u64 tp = links[o0] & 0xFFFFFFFFull, tm = links[o1] & 0xFFFFFFFFull;
+            if ((tp >> 1) != i && (tm >> 1) != i) e = tp < tm ? (tp << 32) | tm : (tm << 32) | tp;
+        }
+        exits[i] = e;
+    }
+}
+
+// Per candidate: the state its + link enters, reversed; the up to four links out of that state lead to the unitigs that enter the
+// same place, i among them; those with i's exit word are its parallels, and kh_pop_beats on their rows gives the popped byte.  The
+// four link words, and then the four exit words, are loaded before any is used; rows only of the parallels.  Seven words of
+// kh_pop_bubbles_into: per-lane sums, one reduction per wave and word, one atomic by its lane 0.
+// kernel-resource-usage (gfx950, hipcc -O3): 88 VGPRs (four link words, four exit words and the unrolled 128-bit products), 88 SGPRs,
+// no LDS, no scratch, no spills, 5 waves per SIMD.
+KH_GLOBAL __launch_bounds__(BLOCK) void pop_decide_kernel(u64 nu, u64 nl, const u64 *__restrict__ rows, const u64 *__restrict__ loff,
+                                                           const u64 *__restrict__ links, const u64 *__restrict__ exits,
+                                                           uint8_t *__restrict__ popped, uint32_t *__restrict__ err, u64 *__restrict__ words) {
+    u64 s_uni = 0, s_links = 0, s_cand = 0, s_pop = 0, s_kmers = 0, s_count = 0, s_bub = 0;
+    bool bad = false;
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < nu; i += (u64)gridDim.x * BLOCK) {
+        const u64 ei = exits[i];
+        const u64 a0 = loff[2 * i];
+        s_uni += 1;
+        s_links += loff[2 * i + 2] - a0;
+        uint32_t po = 0;
+        if (ei != KH_POP_NO_EXITS && a0 >= nl) bad = true;  // (never: pop_exits_kernel saw the same offsets)
+        if (ei != KH_POP_NO_EXITS && a0 < nl) {
+            u64 t = (links[a0] & 0xFFFFFFFFull) ^ 1ull;  // the state its + end enters, reversed
+            if (t >= 2 * nu) {
+                bad = true;
+                t = 2 * i;  // (a state that is there)
+            }
+            const u64 lo = loff[t], hi = loff[t + 1];
+            u64 e = hi - lo;
+            if (lo > hi || e > 4 || hi > nl) {
+                bad = true;
+                e = 0;
+            }
+            const u64 ki = rows[KH_UNI_WORDS * i + KH_UNI_KMERS], si = rows[KH_UNI_WORDS * i + KH_UNI_COUNT_SUM];
+            u64 w[4], ex[4];
+            uint32_t b[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) w[j] = links[j < e ? lo + j : a0];  // (all four link words in flight; a0: a word that is there)
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) b[j] = KH_UNI_LINK_TO(w[j]);
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) ex[j] = exits[b[j] < nu ? (u64)b[j] : i];  // (all four exit words in flight)
+            bool found = false, par = false, beaten = false;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                if (j >= e) continue;
+                if (b[j] == (uint32_t)i) {
+                    found = true;
+                } else if (b[j] >= nu) {
+                    bad = true;
+                } else if (ex[j] == ei) {
+                    par = true;
+                    if (kh_pop_beats(rows[KH_UNI_WORDS * (u64)b[j] + KH_UNI_KMERS], rows[KH_UNI_WORDS * (u64)b[j] + KH_UNI_COUNT_SUM], b[j], ki, si, (uint32_t)i))
+                        beaten = true;
+                }
+            }
+            if (!found) bad = true;  // i is not among the unitigs that enter its own exit
+            po = beaten ? 1u : 0u;
+            s_cand += 1;
+            if (po) {
+                s_pop += 1;
+                s_kmers += ki;
+                s_count += si;
+            } else if (par) {
+                s_bub += 1;
+            }
+        }
+        popped[i] = (uint8_t)po;
+    }
+    if (kh_any(bad) && lane_id() == 0) *err = 1u;
+    s_uni = wave_sum(s_uni);
+    s_links = wave_sum(s_links);
+    s_cand = wave_sum(s_cand);
+    s_pop = wave_sum(s_pop);
+    s_kmers = wave_sum(s_kmers);
+    s_count = wave_sum(s_count);
+    s_bub = wave_sum(s_bub);
+    if (lane_id() == 0) {
+        if (s_uni) atomicAdd(&words[KH_POP_UNITIGS], s_uni);
+        if (s_links) atomicAdd(&words[KH_POP_LINKS], s_links);
+        if (s_cand) atomicAdd(&words[KH_POP_CANDIDATES], s_cand);
+        if (s_pop) atomicAdd(&words[KH_POP_POPPED], s_pop);
+        if (s_kmers) atomicAdd(&words[KH_POP_POPPED_KMERS], s_kmers);
+        if (s_count) atomicAdd(&words[KH_POP_POPPED_COUNT], s_count);
+        if (s_bub) atomicAdd(&words[KH_POP_BUBBLES], s_bub);
+    }
+}
+
 }  // namespace kh
 
 namespace khi {
@@ -599,36 +712,50 @@ int unitig_rank(kh_ctx *c, const uint32_t *next, u64 states, kh::UniRank *cur, k
     return KH_OK;
 }
 
-// kh_clip_tips_into: the target and the rule's bound in, the eight words out.
+// The two rules that remove unitigs behind the links: which pair of decision kernels runs in front of the keep loop.
+enum ClipMode { CLIP_TIPS, CLIP_BUBBLES };
+
+// kh_clip_tips_into / kh_pop_bubbles_into: the rule, the target and the rule's bound in, the eight / nine words out.
 struct ClipJob {
+    ClipMode mode;
     kh_ctx *dst;
     u64 max_kmers;
-    u64 words[KH_CLIP_WORDS];
-    bool on_dst;  // a failure came from dst's side: its text is there already
+    u64 words[KH_POP_WORDS];  // (KH_CLIP_WORDS of them for the tips)
+    bool on_dst;              // a failure came from dst's side: its text is there already
 };
 
-// One round of tip clipping behind the links of c, while unitigs_build's scratch is live: the two decision kernels on c's stream,
-// then the surviving nodes into job->dst on ITS stream, in ranges it has room for (as combine_scan of join.hip).  Every failure
-// before the first insert leaves dst as it was.
+// One round of tip clipping or bubble popping behind the links of c, while unitigs_build's scratch is live: the rule's two decision
+// kernels on c's stream -- they leave one "removed" byte per unitig --, then the surviving nodes into job->dst on ITS stream, in
+// ranges it has room for (as combine_scan of join.hip).  Every failure before the first insert leaves dst as it was.
 int clip_step(kh_ctx *c, ClipJob *job, CallScratch &sc, u64 n, u64 nu, u64 nl, const u64 *keys, const u64 *counts, const uint32_t *order,
               const uint32_t *ordu, const u64 *loff, uint32_t *d_err) {
     kh_ctx *const dst = job->dst;
-    uint8_t *const cand = (uint8_t *)sc.take(nu);
+    const bool pop = job->mode == CLIP_BUBBLES;
+    const u64 nwords = pop ? KH_POP_WORDS : KH_CLIP_WORDS;
+    void *const cand = sc.take(pop ? nu * sizeof(u64) : nu);  // the tips' candidate bytes / the bubbles' exit words
     uint8_t *const clipped = (uint8_t *)sc.take(nu);
-    u64 *const words = (u64 *)sc.take(KH_CLIP_WORDS * sizeof(u64));
-    if (!cand || !clipped || !words) return soft_oom(c, "device memory for the tip clipping's scratch");
-    HIP_TRY(c, hipMemsetAsync(words, 0, KH_CLIP_WORDS * sizeof(u64), c->stream));
-    hipLaunchKernelGGL(kh::clip_candidate_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, job->max_kmers, (const u64 *)c->un.rows, loff,
-                       (const u64 *)c->un.links, cand, d_err);
-    hipLaunchKernelGGL(kh::clip_decide_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, (const u64 *)c->un.rows, loff,
-                       (const u64 *)c->un.links, (const uint8_t *)cand, clipped, d_err, words);
+    u64 *const words = (u64 *)sc.take(nwords * sizeof(u64));
+    if (!cand || !clipped || !words) return soft_oom(c, pop ? "device memory for the bubble popping's scratch" : "device memory for the tip clipping's scratch");
+    HIP_TRY(c, hipMemsetAsync(words, 0, nwords * sizeof(u64), c->stream));
+    if (pop) {
+        hipLaunchKernelGGL(kh::pop_exits_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, job->max_kmers, (const u64 *)c->un.rows, loff,
+                           (const u64 *)c->un.links, (u64 *)cand, d_err);
+        hipLaunchKernelGGL(kh::pop_decide_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, (const u64 *)c->un.rows, loff,
+                           (const u64 *)c->un.links, (const u64 *)cand, clipped, d_err, words);
+    } else {
+        hipLaunchKernelGGL(kh::clip_candidate_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, job->max_kmers, (const u64 *)c->un.rows, loff,
+                           (const u64 *)c->un.links, (uint8_t *)cand, d_err);
+        hipLaunchKernelGGL(kh::clip_decide_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, (const u64 *)c->un.rows, loff,
+                           (const u64 *)c->un.links, (const uint8_t *)cand, clipped, d_err, words);
+    }
     HIP_TRY(c, hipGetLastError());
     uint32_t bad = 0;
     HIP_TRY(c, hipMemcpyAsync(&bad, d_err, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(job->words, words, sizeof(job->words), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(job->words, words, nwords * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the clipped bytes are complete: dst's stream may read them)
     if (bad || job->words[KH_CLIP_UNITIGS] != nu || job->words[KH_CLIP_LINKS] != nl)
-        return fail(c, KH_ERR_STATE, "kh_clip_tips_into: a candidate is not among its own rivals, or the links do not add up (internal error)");
+        return fail(c, KH_ERR_STATE, pop ? "kh_pop_bubbles_into: a candidate is not among the unitigs that enter its own exit, or the links do not add up (internal error)"
+                                         : "kh_clip_tips_into: a candidate is not among its own rivals, or the links do not add up (internal error)");
     int rc = KH_OK;
     job->on_dst = true;
     const u64 step = SUB_TILES * kh::TILE;
@@ -645,14 +772,14 @@ int clip_step(kh_ctx *c, ClipJob *job, CallScratch &sc, u64 n, u64 nu, u64 nl, c
         q0 += m;
     }
     if (rc == KH_OK && hipMemcpyAsync(job->words + KH_CLIP_KEPT_KMERS, words + KH_CLIP_KEPT_KMERS, 2 * sizeof(u64), hipMemcpyDeviceToHost, dst->stream) != hipSuccess)
-        rc = fail(dst, KH_ERR_HIP, "kh_clip_tips_into: the kept words");
+        rc = fail(dst, KH_ERR_HIP, pop ? "kh_pop_bubbles_into: the kept words" : "kh_clip_tips_into: the kept words");
     if (rc == KH_OK) rc = sync_counters(dst);  // (complete when it returns; an upsert without a free slot shows here)
     else (void)hipStreamSynchronize(dst->stream);  // (before the scratch goes back)
     return rc;
 }
 
 // linked: kh_unitigs_begin_linked -- the link array behind the same kernels; nothing of it is launched or allocated without.
-// clip: kh_clip_tips_into -- linked, without the base array, and clip_step() behind the links.
+// clip: kh_clip_tips_into / kh_pop_bubbles_into -- linked, without the base array, and clip_step() behind the links.
 int unitigs_build(kh_ctx *c, u64 n, u64 mc, CallScratch &sc, bool linked, ClipJob *clip = nullptr) {
     const uint32_t n32 = (uint32_t)n, k = c->k;
     const u64 states = 2 * n;
@@ -851,15 +978,19 @@ extern "C" int kh_unitigs_begin_linked(kh_ctx *c, uint64_t min_count, uint64_t *
     return unitigs_begin(c, "kh_unitigs_begin_linked", min_count, n_unitigs, n_bases, n_links, true);
 }
 
-// src's unitigs and links are built as kh_unitigs_begin_linked builds them (without the bases), decided and handed on while the
-// scratch is live, and released again: nothing of them outlives the call.
-extern "C" int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out) {
+namespace khi {
+namespace {
+
+// kh_clip_tips_into and kh_pop_bubbles_into: src's unitigs and links are built as kh_unitigs_begin_linked builds them (without the
+// bases), decided by the rule of `mode` and handed on while the scratch is live, and released again: nothing of them outlives the call.
+int clip_into(const char *who, ClipMode mode, kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out) {
     if (!dst) return KH_ERR_BAD_ARG;
-    if (!src || !out) return fail(dst, KH_ERR_BAD_ARG, "kh_clip_tips_into: NULL argument");
-    if (dst == src) return fail(dst, KH_ERR_BAD_ARG, "kh_clip_tips_into: dst must not be src");
-    int rc = join_check(dst, "kh_clip_tips_into", src, nullptr, dst);
+    const std::string w(who);
+    if (!src || !out) return fail(dst, KH_ERR_BAD_ARG, (w + ": NULL argument").c_str());
+    if (dst == src) return fail(dst, KH_ERR_BAD_ARG, (w + ": dst must not be src").c_str());
+    int rc = join_check(dst, who, src, nullptr, dst);
     if (rc != KH_OK) return rc;
-    if (src->shard_shift) return fail(dst, KH_ERR_STATE, "kh_clip_tips_into: the table is a shard; its k-mers' neighbours live on other owners");
+    if (src->shard_shift) return fail(dst, KH_ERR_STATE, (w + ": the table is a shard; its k-mers' neighbours live on other owners").c_str());
     auto from_src = [&](int r) {  // (the error text is on dst)
         if (r != KH_OK) dst->last_error = src->last_error;
         return r;
@@ -870,8 +1001,8 @@ extern "C" int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, u
     const u64 mc = min_count ? min_count : 1;
     uint64_t n = 0;
     if ((rc = kh_result_size(src, mc, &n)) != KH_OK) return from_src(rc);
-    if (n > 0x7FFFFFFFull) return fail(dst, KH_ERR_RANGE, "kh_clip_tips_into: more than 2^31 - 1 nodes: node ids are 32-bit");
-    ClipJob job{dst, max_kmers, {0, 0, 0, 0, 0, 0, 0, 0}, false};
+    if (n > 0x7FFFFFFFull) return fail(dst, KH_ERR_RANGE, (w + ": more than 2^31 - 1 nodes: node ids are 32-bit").c_str());
+    ClipJob job{mode, dst, max_kmers, {0, 0, 0, 0, 0, 0, 0, 0, 0}, false};
     if (n) {
         {
             CallScratch sc(src);
@@ -884,8 +1015,19 @@ extern "C" int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, u
         unitigs_release(src);
         if (rc != KH_OK) return job.on_dst ? rc : from_src(rc);
     }
-    memcpy(out, job.words, sizeof(job.words));
+    memcpy(out, job.words, (mode == CLIP_BUBBLES ? KH_POP_WORDS : KH_CLIP_WORDS) * sizeof(u64));
     return KH_OK;
+}
+
+}  // namespace
+}  // namespace khi
+
+extern "C" int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out) {
+    return clip_into("kh_clip_tips_into", CLIP_TIPS, dst, src, min_count, max_kmers, out);
+}
+
+extern "C" int kh_pop_bubbles_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out) {
+    return clip_into("kh_pop_bubbles_into", CLIP_BUBBLES, dst, src, min_count, max_kmers, out);
 }
 
 extern "C" int kh_unitigs_links_copy_device(kh_ctx *c, uint64_t *d_links, uint64_t cap) {

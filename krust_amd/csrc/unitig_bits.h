@@ -1,6 +1,7 @@
 // unitig_bits.h -- the oriented-successor arithmetic of the unitig construction (include/kmerhip.h, "unitigs of a count table"),
 // shared by unitig.hip and by a plain host compiler (tests/unitig_bits_check.cpp compares it with string arithmetic for every k,
-// tests/unitig_links_check.cpp the link word and the enter sign, tests/clip_bits_check.cpp the tip-clipping comparator at the end of this file).
+// tests/unitig_links_check.cpp the link word and the enter sign, tests/clip_bits_check.cpp the tip-clipping comparator and
+// tests/pop_bits_check.cpp the bubble-popping comparator at the end of this file).
 //
 // An oriented node is (x, sign): sign 0 = (x, +) spells x's canonical string s, sign 1 = (x, -) spells rc(s).  As a state number it
 // is 2 * id + sign with id = the rank of x among the nodes, so rev() is ^ 1.
@@ -68,5 +69,28 @@ KH_HD bool kh_clip_beats(uint64_t kmers_b, uint64_t sum_b, uint32_t idx_b, bool 
     if (!cand_b) return true;
     if (kmers_b != kmers_i) return kmers_b > kmers_i;
     if (sum_b != sum_i) return sum_b > sum_i;
+    return idx_b < idx_i;
+}
+
+// ---- bubble popping (include/kmerhip.h, kh_pop_bubbles_into; tests/pop_bits_check.cpp) -----------------------------------------------
+// a * b as (hi, lo), from the four products of the 32-bit halves: the same text for the device and for a plain host compiler.
+KH_HD void kh_mul_64x64(uint64_t a, uint64_t b, uint64_t *hi, uint64_t *lo) {
+    const uint64_t a0 = a & 0xFFFFFFFFull, a1 = a >> 32, b0 = b & 0xFFFFFFFFull, b1 = b >> 32;
+    const uint64_t p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
+    const uint64_t mid = (p00 >> 32) + (p01 & 0xFFFFFFFFull) + (p10 & 0xFFFFFFFFull);  // (below 3 * 2^32)
+    *lo = (p00 & 0xFFFFFFFFull) | (mid << 32);
+    *hi = p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);  // (the product is below 2^128: no carry out)
+}
+
+// Whether parallel candidate b beats candidate i (b != i): by the greater mean count COUNT_SUM / KMERS, compared exactly as the
+// 128-bit products COUNT_SUM_b * KMERS_i and COUNT_SUM_i * KMERS_b (the sums as the rows store them), then by the greater KMERS,
+// then by the smaller index.
+KH_HD bool kh_pop_beats(uint64_t kmers_b, uint64_t sum_b, uint32_t idx_b, uint64_t kmers_i, uint64_t sum_i, uint32_t idx_i) {
+    uint64_t bh, bl, ih, il;
+    kh_mul_64x64(sum_b, kmers_i, &bh, &bl);
+    kh_mul_64x64(sum_i, kmers_b, &ih, &il);
+    if (bh != ih) return bh > ih;
+    if (bl != il) return bl > il;
+    if (kmers_b != kmers_i) return kmers_b > kmers_i;
     return idx_b < idx_i;
 }

@@ -88,6 +88,11 @@ CLIP_WORDS = 8
 CLIP_UNITIGS, CLIP_CANDIDATES, CLIP_CLIPPED, CLIP_CLIPPED_KMERS, CLIP_CLIPPED_COUNT, CLIP_KEPT_KMERS, CLIP_KEPT_COUNT, CLIP_LINKS = range(8)
 CLIP_NAMES = ("unitigs", "candidates", "clipped", "clipped_kmers", "clipped_count", "kept_kmers", "kept_count", "links")
 
+# KH_POP_*: the words of kh_pop_bubbles_into
+POP_WORDS = 9
+POP_UNITIGS, POP_CANDIDATES, POP_POPPED, POP_POPPED_KMERS, POP_POPPED_COUNT, POP_KEPT_KMERS, POP_KEPT_COUNT, POP_LINKS, POP_BUBBLES = range(9)
+POP_NAMES = ("unitigs", "candidates", "popped", "popped_kmers", "popped_count", "kept_kmers", "kept_count", "links", "bubbles")
+
 
 _SET_OPS = {"intersect": SET_INTERSECT, "union": SET_UNION, "subtract": SET_SUBTRACT, "count-subtract": SET_COUNT_SUBTRACT}
 _CALCS = {"min": CALC_MIN, "max": CALC_MAX, "sum": CALC_SUM, "left": CALC_LEFT, "right": CALC_RIGHT}
@@ -165,6 +170,7 @@ SYMBOLS = {
     "kh_unitigs_links_copy_device": (C.c_int, [_P, _P, _U64]),
     "kh_unitigs_links_copy": (C.c_int, [_P, _P, _U64]),
     "kh_clip_tips_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
+    "kh_pop_bubbles_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
     "kh_set_shard": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "kh_set_region_window": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -642,6 +648,20 @@ class DeviceCounter:
         mk = self.k if max_kmers is None else int(max_kmers)
         self._check(lib().kh_clip_tips_into(self._h, src._h, int(min_count), mk, out.ctypes.data))
         return dict(zip(CLIP_NAMES, (int(x) for x in out)))
+
+    # -- bubble popping: one round over the compacted graph --------------------
+    def pop_bubbles_into(self, src, min_count=1, max_kmers=None):
+        """kh_pop_bubbles_into: one round of bubble popping of `src`'s compacted graph at min_count -- the k-mers of every surviving
+        unitig are added to THIS table with their counts from src (count[key] += c).  Non-circular unitigs of at most max_kmers
+        k-mers (None: 2 * k; the branch of a SNP has k) with one link out of each end are parallel when the two ends enter the
+        same pair of states; of each such class only the one with the greatest mean count stays (then the most k-mers, then the
+        smallest index: include/kmerhip.h).  src's table is only read, unitigs it had begun are released; this table must not be
+        src.  Returns the nine words as a dict: unitigs, candidates, popped, popped_kmers, popped_count, kept_kmers, kept_count,
+        links, bubbles."""
+        out = np.zeros(POP_WORDS, dtype=np.uint64)
+        mk = 2 * self.k if max_kmers is None else int(max_kmers)
+        self._check(lib().kh_pop_bubbles_into(self._h, src._h, int(min_count), mk, out.ctypes.data))
+        return dict(zip(POP_NAMES, (int(x) for x in out)))
 
     # -- multi-GPU merge ---------------------------------------------------
     def comm_init(self, nranks, rank, unique_id):

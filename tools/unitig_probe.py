@@ -17,6 +17,11 @@ With --clip, per size and in one process, only these two, on the same table:
   unitigs_begin_linked kh_unitigs_begin_linked(1), as above
   clip_tips_into       kh_clip_tips_into(1, max_kmers = k) into a fresh context hinted with the node count, kh_reset (not timed)
                        before every call; clip_share = the part of its median that is not unitigs_begin_linked's; the eight words beside it
+With --pop, per size and in one process, these three, on the same table:
+  unitigs_begin_linked kh_unitigs_begin_linked(1), as above
+  clip_tips_into       kh_clip_tips_into(1, max_kmers = k), as with --clip
+  pop_bubbles_into     kh_pop_bubbles_into(1, max_kmers = 2 k) into the same fresh context, kh_reset (not timed) before every call;
+                       pop_share = the part of its median that is not unitigs_begin_linked's; the nine words beside it
 The measurement runs in a child process with a timeout; a failure is reported as {"error": ...}."""
 import argparse
 import json
@@ -100,7 +105,7 @@ def measure_one(n, k):
     return out
 
 
-def measure_clip_one(n, k):
+def measure_clip_one(n, k, pop=False):
     import torch
     from krust_amd import native
     rl = 150
@@ -133,13 +138,29 @@ def measure_clip_one(n, k):
     assert sb["distinct"] == got["words"]["kept_kmers"] and sb["kmers"] == got["words"]["kept_count"]
     assert got["words"]["kept_kmers"] + got["words"]["clipped_kmers"] == nodes and a.finish()["distinct"] == nodes
     out["dst_grows"] = sb["grows"]
+    if pop:
+        ts = []
+        for rep in range(6):                  # one warm call, then five
+            b.reset()
+            t0 = time.perf_counter()
+            got["pop"] = b.pop_bubbles_into(a, 1, 2 * k)
+            ts.append(time.perf_counter() - t0)
+        ts = sorted(ts[1:])
+        popt = {"median_s": ts[len(ts) // 2], "spread_s": ts[-1] - ts[0]}
+        out["pop_bubbles_into"] = dict(rate(popt), pop_share=max(popt["median_s"] - linked["median_s"], 0.0) / popt["median_s"])
+        out["pop_words"] = got["pop"]
+        sb = b.finish()
+        assert sb["distinct"] == got["pop"]["kept_kmers"] and sb["kmers"] == got["pop"]["kept_count"]
+        assert got["pop"]["kept_kmers"] + got["pop"]["popped_kmers"] == nodes and a.finish()["distinct"] == nodes
+        assert got["pop"]["unitigs"] == got["words"]["unitigs"] and got["pop"]["links"] == got["words"]["links"]
+        out["pop_dst_grows"] = sb["grows"]
     b.close()
     a.close()
     return out
 
 
 def measure(args):
-    one = measure_clip_one if args.clip else measure_one
+    one = (lambda n, k: measure_clip_one(n, k, pop=True)) if args.pop else measure_clip_one if args.clip else measure_one
     print("RESULT " + json.dumps([one(n, args.k) for n in args.reads]))
 
 
@@ -149,19 +170,20 @@ def main():
     ap.add_argument("--k", type=int, default=21)
     ap.add_argument("--timeout", type=int, default=900)
     ap.add_argument("--clip", action="store_true", help="kh_clip_tips_into beside kh_unitigs_begin_linked, nothing else")
+    ap.add_argument("--pop", action="store_true", help="kh_pop_bubbles_into beside kh_clip_tips_into and kh_unitigs_begin_linked, nothing else")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
         measure(args)
         return
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k)] + (["--clip"] if args.clip else []) + ["--reads"] + [str(n) for n in args.reads]
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k)] + (["--clip"] if args.clip else []) + (["--pop"] if args.pop else []) + ["--reads"] + [str(n) for n in args.reads]
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
         line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
         res = json.loads(line[-1][7:]) if p.returncode == 0 and line else {"error": f"exit {p.returncode}", "stderr": p.stderr[-2000:]}
     except subprocess.TimeoutExpired:
         res = {"error": f"no result within {args.timeout} s"}
-    print(json.dumps({"probe": "unitig-clip" if args.clip else "unitig", "result": res}, indent=1))
+    print(json.dumps({"probe": "unitig-pop" if args.pop else "unitig-clip" if args.clip else "unitig", "result": res}, indent=1))
 
 
 if __name__ == "__main__":
