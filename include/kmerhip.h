@@ -701,7 +701,10 @@ int kh_merge_pairs(kh_ctx *ctx, const uint64_t *keys, const uint64_t *counts, ui
  * shard (a finished merge leaves every rank one, so that refusal is collective by itself).  Every wait is bounded by KMERHIP_MERGE_TIMEOUT_S (default 300 s): on expiry, or on
  * an asynchronous RCCL error, the communicator is aborted (ncclCommAbort) and the call returns KH_ERR_RCCL; that
  * context's communicator is dead afterwards (kh_merge_across refuses it; make a new context and communicator).
- * After any failed merge the table's content is unspecified until kh_reset. */
+ * After any failed merge the table's content is unspecified until kh_reset.
+ * ONE RANK (a communicator of one, or no communicator at all): shard 0 of 1 is the whole hash range, so the context is left a
+ * FULL table with the content it had -- kh_push*, kh_graph_*, kh_unitigs_* and a further kh_merge_across are accepted as
+ * before, nothing is refused. */
 typedef struct kh_unique_id { char internal[128]; } kh_unique_id;  /* ncclUniqueId, opaque */
 int kh_comm_unique_id(kh_unique_id *out);
 /* Collective over all ranks (it blocks until every rank has called it).  The context must be on the GPU this
