@@ -128,6 +128,9 @@ pub mod sys {
         pub fn kh_unitigs_begin_linked(ctx: *mut KhCtx, min_count: u64, n_unitigs: *mut u64, n_bases: *mut u64, n_links: *mut u64) -> c_int;
         pub fn kh_unitigs_links_copy_device(ctx: *mut KhCtx, d_links: *mut u64, cap: u64) -> c_int;
         pub fn kh_unitigs_links_copy(ctx: *mut KhCtx, links: *mut u64, cap: u64) -> c_int;
+        pub fn kh_unitigs_text_begin(ctx: *mut KhCtx, format: u32, n_bytes: *mut u64) -> c_int;
+        pub fn kh_unitigs_text_next(ctx: *mut KhCtx, buf: *mut u8, cap: u64, n: *mut u64) -> c_int;
+        pub fn kh_unitigs_text_next_device(ctx: *mut KhCtx, d_buf: *mut u8, cap: u64, n: *mut u64) -> c_int;
         /// one round of tip clipping of `src`'s compacted graph at `min_count`: the k-mers of the surviving unitigs are added to `dst`
         /// (`count[key] += c`); `out` takes the 8 words KH_CLIP_* of the header names
         pub fn kh_clip_tips_into(dst: *mut KhCtx, src: *mut KhCtx, min_count: u64, max_kmers: u64, out: *mut u64) -> c_int;
@@ -228,6 +231,9 @@ pub const UNI_FLAGS: usize = 3;
 /// `KH_UNI_CIRCULAR`: bit 0 of the flags word -- the chain closes, and the closing overlap is not repeated in the bases.
 pub const UNI_CIRCULAR: u64 = 1;
 
+/// `KH_UNI_TEXT_FASTA` / `KH_UNI_TEXT_GFA`: the formats of [`HipKmerMap::unitigs_text`].
+pub const UNI_TEXT_FASTA: u32 = 1;
+pub const UNI_TEXT_GFA: u32 = 2;
 /// `KH_UNI_LINK_FROM(w)`: the unitig a link word of `kh_unitigs_links_copy` leaves (a row index of `kh_unitigs_copy`).
 pub const fn uni_link_from(w: u64) -> u32 { (w >> 33) as u32 }
 /// `KH_UNI_LINK_FROM_SIGN(w)`: 0 = it leaves the right end of the reported sequence (+), 1 = that of its reverse complement (-).
@@ -608,6 +614,39 @@ impl HipKmerMap {
         check(self.ctx, rl)?;
         check(self.ctx, end)?;
         Ok((rows, bases, links))
+    }
+
+    /// The unitigs of the table as text, formatted on the device (`kh_unitigs_begin[_linked]` / `kh_unitigs_text_begin` /
+    /// `kh_unitigs_text_next` / `kh_unitigs_end`): [`UNI_TEXT_FASTA`] is what `kmerust unitigs -f fasta` prints, [`UNI_TEXT_GFA`]
+    /// what `kmerust gfa -f gfa` prints (segments, then one L line per link).  Only text crosses the link, in pieces of up to
+    /// 64 MiB.
+    pub fn unitigs_text(&self, format: u32, min_count: u64) -> Result<Vec<u8>, HipError> {
+        let (mut nu, mut nb, mut nl, mut total) = (0u64, 0u64, 0u64, 0u64);
+        check(self.ctx, unsafe {
+            if format == UNI_TEXT_GFA {
+                sys::kh_unitigs_begin_linked(self.ctx, min_count, &mut nu, &mut nb, &mut nl)
+            } else {
+                sys::kh_unitigs_begin(self.ctx, min_count, &mut nu, &mut nb)
+            }
+        })?;
+        let mut rc = unsafe { sys::kh_unitigs_text_begin(self.ctx, format, &mut total) };
+        let mut text = vec![0u8; if rc == 0 { total as usize } else { 0 }];
+        let mut at = 0usize;
+        while rc == 0 && at < text.len() {
+            let mut n = 0u64;
+            let cap = (text.len() - at).min(64 << 20) as u64;
+            rc = unsafe { sys::kh_unitigs_text_next(self.ctx, text.as_mut_ptr().add(at), cap, &mut n) };
+            if n == 0 {
+                break;
+            }
+            at += n as usize;
+        }
+        let err = check(self.ctx, rc);  // (before kh_unitigs_end replaces the error text)
+        let end = unsafe { sys::kh_unitigs_end(self.ctx) };
+        err?;
+        check(self.ctx, end)?;
+        text.truncate(at);
+        Ok(text)
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

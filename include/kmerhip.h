@@ -68,12 +68,13 @@ typedef enum kh_status {
 
 /* Allocation failures: what KH_ERR_OOM leaves behind.  One rule per kind of call; the comments further down only add to it.
  *   - A READING call takes the table as it is and allocates only for itself: kh_result_size / _copy / _copy_device / _sorted*,
- *     kh_result_text_*, kh_histogram, kh_lookup, kh_profile*, kh_profile_records*, kh_compare, kh_graph_*, kh_unitigs_* and the
- *     src side of kh_clip_tips_into / kh_pop_bubbles_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
+ *     kh_result_text_*, kh_histogram, kh_lookup, kh_profile*, kh_profile_records*, kh_compare, kh_graph_*, kh_unitigs_*,
+ *     kh_unitigs_text_begin / kh_unitigs_text_next / kh_unitigs_text_next_device and the src side of kh_clip_tips_into / kh_pop_bubbles_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
  *     allocation, the table is unchanged and the context is NOT poisoned: the same call can be made again.  What the call
  *     allocated is released, except the scratch the context keeps for the next such call where that had been allocated
  *     before the failure: the pinned staging chunks and the copy stream of the host forms, the scan scratch (not after the
- *     sorted results, kh_unitigs_begin*, kh_clip_tips_into and kh_pop_bubbles_into: there nothing stays), the tile arrays of a text stream, the
+ *     sorted results, kh_unitigs_begin*, kh_clip_tips_into and kh_pop_bubbles_into: there nothing stays), the tile arrays of a text stream (a failure of kh_unitigs_text_begin / kh_unitigs_text_next /
+ *     kh_unitigs_text_next_device ends that stream and releases its offsets and chunks; the unitigs stay live), the
  *     chunk and row buffers of kh_profile / kh_profile_records, the words of kh_compare and kh_graph_stats.  kh_destroy
  *     releases them.  (Pushes that were still pending when the reading call came are counted first, as a writing call.)
  *   - A WRITING call changes the table: the pushes and the counting they trigger (also when a later call counts them), growth,
@@ -502,6 +503,38 @@ int kh_unitigs_end(kh_ctx *ctx);
 int kh_unitigs_begin_linked(kh_ctx *ctx, uint64_t min_count, uint64_t *n_unitigs, uint64_t *n_bases, uint64_t *n_links);
 int kh_unitigs_links_copy_device(kh_ctx *ctx, uint64_t *d_links, uint64_t cap);
 int kh_unitigs_links_copy(kh_ctx *ctx, uint64_t *links, uint64_t cap);
+
+/* ---- the live unitigs as TEXT, formatted on the device (what `kmerust unitigs -f fasta` and `kmerust gfa -f gfa` print) ----- */
+/* With i the row index, L = KMERS, cs = COUNT_SUM, seq the unitig's L + k - 1 bases and km = what "%.1f" prints of
+ * (double)cs / (double)L (0.0 for L = 0):
+ *   KH_UNI_TEXT_FASTA  per unitig  >{i} LN:i:{L+k-1} KC:i:{cs} km:f:{km}[ CR:i:1]\n{seq}\n       (CR:i:1: KH_UNI_CIRCULAR)
+ *                      no unitigs: 0 bytes
+ *   KH_UNI_TEXT_GFA    first       H\tVN:Z:1.0\n
+ *                      per unitig  S\t{i}\t{seq}\tLN:i:{L+k-1}\tKC:i:{cs}\tkm:f:{km}[\tCR:i:1]\n
+ *                      per link word, in array order  L\t{from}\t{+|-}\t{to}\t{+|-}\t{k-1}M\n
+ *                      no unitigs: the header line alone.  Needs kh_unitigs_begin_linked.
+ * A pull interface like kh_result_text_*: kh_unitigs_text_begin sizes the document (*n_bytes: its length, may be NULL), every
+ * kh_unitigs_text_next* hands out the next piece.  A unitig has no length bound, so a piece is a BYTE RANGE, not whole lines:
+ *   - next writes *n = min(cap, bytes left); *n = 0 with KH_OK says that the stream has ended.  cap = 0 while bytes are left is
+ *     KH_ERR_RANGE and consumes nothing.  A NULL n, or a NULL buffer with cap > 0, is KH_ERR_BAD_ARG.
+ *   - The concatenation of the pieces is the same document for EVERY sequence of cap values, and the same table content gives
+ *     the same bytes for every geometry and table form (as the rows, bases and links do).
+ *   - kh_unitigs_text_next takes pageable memory, or memory of kh_host_alloc / kh_host_register; the next chunk (up to 64 MiB) is
+ *     formatted while the current one travels.  kh_unitigs_text_next_device writes device memory of this context's device at
+ *     any alignment, nothing at or behind d_buf[*n], and is complete when it returns.
+ *   - begin enters as a reader; the stream belongs to the live unitigs and ends with kh_unitigs_end, the next begin of either
+ *     kind, kh_reset / kh_destroy and every call that makes the unitigs stale.  KH_ERR_STATE: begin without live unitigs,
+ *     KH_UNI_TEXT_GFA after a plain kh_unitigs_begin (the message names kh_unitigs_begin_linked), next without a running stream.
+ *     KH_ERR_BAD_ARG: an unknown format.  begin on a running stream restarts it.
+ *   - Every reader may come between two next calls -- kh_unitigs_copy*, kh_unitigs_links_copy*, a whole kh_result_text_* stream:
+ *     the two streams share no memory (the chunks here are the stream's own, never the partition buffers).
+ *   - KH_ERR_OOM follows the rule of the reading calls: the context is not poisoned, the unitigs stay live, no stream is on and
+ *     what the stream had allocated is released -- begin again. */
+#define KH_UNI_TEXT_FASTA 1   /* the bytes `kmerust unitigs -f fasta` prints */
+#define KH_UNI_TEXT_GFA   2   /* the bytes `kmerust gfa -f gfa` prints; needs kh_unitigs_begin_linked */
+int kh_unitigs_text_begin(kh_ctx *ctx, uint32_t format, uint64_t *n_bytes /* may be NULL */);
+int kh_unitigs_text_next(kh_ctx *ctx, uint8_t *buf, uint64_t cap, uint64_t *n);
+int kh_unitigs_text_next_device(kh_ctx *ctx, uint8_t *d_buf, uint64_t cap, uint64_t *n);
 
 /* ---- tip clipping: one round of removing short dead-end branches (what assemblers do first with the compacted graph) --- */
 /* Take the unitigs and links of kh_unitigs_begin_linked(src, min_count): rows, end states (i, +) and (i, -) and link words exactly

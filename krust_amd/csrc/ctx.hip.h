@@ -10,6 +10,7 @@
 //   join.hip      kh_compare / kh_combine_into: one table scanned, another probed, statistics or a third table out
 //   graph.hip     kh_graph_stats / kh_graph_masks*: the table against itself, eight probes per k-mer, its de Bruijn degrees out
 //   unitig.hip    kh_unitigs_*: the maximal non-branching paths of that graph (link rule, chain ranking by pointer doubling, emitter, links between them)
+//   unitig_text.hip  kh_unitigs_text_*: those unitigs and links as FASTA / GFA text, formatted on the device and streamed out in pieces
 //   sort.hip      kh_result_sorted*: the result pairs in ascending key order (a device radix sort; format.hip streams it as text)
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
@@ -122,6 +123,7 @@ struct Knobs {
     u64 table_room_mb = 0;           // KMERHIP_TABLE_ROOM_MB: what the sample-sized table may take, as if the device had no more
     bool stop_after_p1 = false, stop_after_p2 = false;  // ablation builds (KH_ABL*)
     u64 profile_chunk_kb = 0;        // KMERHIP_PROFILE_CHUNK_KB: window starts per chunk of kh_profile, in units of 1024 (0: sized from the call)
+    u64 uni_text_chunk_kb = 0;       // KMERHIP_UNI_TEXT_CHUNK_KB: bytes per chunk of kh_unitigs_text_next*, in KiB, rounded up to whole tiles (0: up to 64 MiB)
     // KMERHIP_ALLOC_FAIL=n | n+, KMERHIP_ALLOC_TRACE=path: the n-th allocation through dev_malloc / pin_malloc (below) fails; every
     // allocation, release and injected failure is appended to a file.  Not fields: read at every allocation, one count per process.
     // KMERHIP_GRID_CAP: the most workgroups of a capped-grid launch (0 / unset: GRID_CAP).  Not a field: one value per process,
@@ -403,6 +405,26 @@ struct kh_ctx {
         bool linked = false;      // built by kh_unitigs_begin_linked: the link words, one per (end state, successor)
         u64 *links = nullptr;     // (nullptr when there are none)
         u64 n_links = 0;
+        // kh_unitigs_text_* (unitig_text.hip): these unitigs as text.  begin sizes every record and link line and scans both; next formats
+        // ranges of whole tiles of UT_TILE bytes into one of two device chunks of the stream's OWN -- never the partition buffers: a
+        // kh_result_text_* stream may run beside it -- and hands their bytes out: chunk i + 1 is formatted on `stream` while chunk i
+        // travels on `cstream`.  Running = live && text.on; unitigs_release() gives its memory back with the unitigs'.
+        struct Text {
+            bool on = false;
+            uint32_t format = 0;
+            u64 hdr = 0, rec_bytes = 0, link_bytes = 0, total = 0;  // the GFA header, the records, the link lines; their sum
+            u64 *off = nullptr;                    // device: n_unitigs + 1 record offsets, then n_links + 1 link-line offsets (gfa with links only)
+            u64 chunk_bytes = 0;                   // whole tiles
+            u64 next_off = 0;                      // first byte of the document no chunk holds yet (a multiple of UT_TILE, or total)
+            u64 sent = 0;                          // bytes handed out
+            struct Chunk {
+                uint8_t *d = nullptr;
+                u64 len = 0, pos = 0;           // bytes it holds / has handed out
+                bool valid = false;
+                hipEvent_t done = nullptr;      // its formatting kernel (on `stream`)
+            } ch[2];
+            int cur = 0;                           // the chunk being handed out
+        } text;
     } un;
 
     bool poisoned = false;
@@ -564,6 +586,9 @@ int sorted_into(kh_ctx *c, u64 *out_keys, u64 *out_counts, u64 n, u64 min_count,
 int join_check(kh_ctx *err, const char *who, const kh_ctx *a, const kh_ctx *b, const kh_ctx *dst);
 // ---- unitig.hip
 void unitigs_release(kh_ctx *c);  // kh_unitigs_end / kh_reset / kh_destroy: the rows, bases and links of the last kh_unitigs_begin[_linked]
+inline unsigned uni_grid(u64 items) { return (unsigned)grid_for(items); }  // every launch of unitig.hip and unitig_text.hip: KMERHIP_GRID_CAP applies
+// ---- unitig_text.hip
+void unitigs_text_release(kh_ctx *c);  // the offsets, chunks and events of a kh_unitigs_text_* stream (unitigs_release calls it)
 // ---- profile.hip
 void profile_release(kh_ctx *c);  // kh_destroy: the chunk buffers and events of kh_profile, the rows of kh_profile_records
 

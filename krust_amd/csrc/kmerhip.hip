@@ -69,6 +69,7 @@ void read_knobs(Knobs &k) {
     k.stop_after_p1 = env_of("KMERHIP_STOP_AFTER_P1") != nullptr;
     k.stop_after_p2 = env_of("KMERHIP_STOP_AFTER_P2") != nullptr;
     if (const char *e = env_of("KMERHIP_PROFILE_CHUNK_KB")) k.profile_chunk_kb = strtoull(e, nullptr, 10);
+    if (const char *e = env_of("KMERHIP_UNI_TEXT_CHUNK_KB")) k.uni_text_chunk_kb = strtoull(e, nullptr, 10);
     const char *gc = env_of("KMERHIP_GRID_CAP");
     const int cap = gc ? atoi(gc) : 0;
     g_grid_cap.store((cap > 0 && cap < GRID_CAP) ? cap : GRID_CAP, std::memory_order_relaxed);

@@ -678,6 +678,7 @@ KH_GLOBAL __launch_bounds__(BLOCK) void pop_decide_kernel(u64 nu, u64 nl, const 
 namespace khi {
 
 void unitigs_release(kh_ctx *c) {
+    unitigs_text_release(c);  // (a text stream belongs to these unitigs)
     if (c->un.rows) (void)dev_free(c->un.rows);  // (synchronises the device)
     if (c->un.bases) (void)dev_free(c->un.bases);
     if (c->un.links) (void)dev_free(c->un.links);
@@ -685,8 +686,6 @@ void unitigs_release(kh_ctx *c) {
 }
 
 namespace {
-
-unsigned uni_grid(u64 items) { return (unsigned)grid_for(items); }
 
 // The chain ranking over `states` states: init into *cur, then rounds that ping-pong between *cur and *oth until nothing changes
 // or the bound is reached.  *open = the last round still changed something: states on cycles.

@@ -207,6 +207,22 @@ static int run_two_indexes(const Args &args, bool combine) {
 static int run_compare(const Args &args) { return run_two_indexes(args, false); }
 static int run_combine(const Args &args) { return run_two_indexes(args, true); }
 
+// KMERUST_TIMING=1: one JSON line on stderr when the command is done (bench.py's `cli` leg reads the count command's; `unitigs` and
+// `gfa` print the same line: result_s = the unitigs' construction and the text's sizing, write_s = the text, writer = who formatted it)
+struct TimingPrinter {
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    ~TimingPrinter() {
+        const char *e = getenv("KMERUST_TIMING");
+        if (!e || !e[0] || e[0] == '0') return;
+        const Timing &t = timing();
+        const double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        fprintf(stderr, "{\"kmerust_timing\": {\"total_s\": %.6f, \"create_s\": %.6f, \"read_s\": %.6f, \"push_s\": %.6f, \"finish_s\": %.6f, "
+                        "\"result_s\": %.6f, \"write_s\": %.6f, \"buffers_s\": %.6f, \"destroy_s\": %.6f, \"bytes_read\": %llu, \"chunks\": %llu, \"device_record_scan\": %s, \"writer\": \"%s\"}}\n",
+                total, t.create_s, t.read_s, t.push_s, t.finish_s, t.result_s, t.write_s, t.buffers_s, t.destroy_s, (unsigned long long)t.bytes_read,
+                (unsigned long long)t.chunks, t.text_path ? "true" : "false", t.device_writer ? "device" : "host");
+    }
+};
+
 // kmerust graph / unitigs / gfa <INDEX> ...: the de Bruijn graph of an index, its unitigs, and the links between them (no reference
 // counterpart)
 static int run_graph(const Args &args) {
@@ -217,11 +233,13 @@ static int run_graph(const Args &args) {
 static int run_unitigs(const Args &args) {
     const IndexArgs a = parse_unitigs_args(args);
     if (!a.error.empty()) usage_error(a.error);
+    TimingPrinter timing_printer;
     return run_guarded("unitigs: ", [&] { return unitigs_index(a.index, a.min_count, (UnitigFormat)a.format, stdout), 0; });
 }
 static int run_gfa(const Args &args) {
     const IndexArgs a = parse_gfa_args(args);
     if (!a.error.empty()) usage_error(a.error);
+    TimingPrinter timing_printer;
     return run_guarded("gfa: ", [&] { return gfa_index(a.index, a.min_count, (GfaFormat)a.format, stdout), 0; });
 }
 
@@ -319,20 +337,7 @@ static int run_count(const Args &args) {
                      a.save.empty() ? "" : "save-index: " + a.save + "\n"))
         return 1;
 
-    const auto t_begin = std::chrono::steady_clock::now();
-    struct TimingPrinter {  // KMERUST_TIMING=1: one JSON line on stderr when the command is done (bench.py's `cli` leg reads it)
-        std::chrono::steady_clock::time_point t0;
-        ~TimingPrinter() {
-            const char *e = getenv("KMERUST_TIMING");
-            if (!e || !e[0] || e[0] == '0') return;
-            const Timing &t = timing();
-            const double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            fprintf(stderr, "{\"kmerust_timing\": {\"total_s\": %.6f, \"create_s\": %.6f, \"read_s\": %.6f, \"push_s\": %.6f, \"finish_s\": %.6f, "
-                            "\"result_s\": %.6f, \"write_s\": %.6f, \"buffers_s\": %.6f, \"destroy_s\": %.6f, \"bytes_read\": %llu, \"chunks\": %llu, \"device_record_scan\": %s, \"writer\": \"%s\"}}\n",
-                    total, t.create_s, t.read_s, t.push_s, t.finish_s, t.result_s, t.write_s, t.buffers_s, t.destroy_s, (unsigned long long)t.bytes_read,
-                    (unsigned long long)t.chunks, t.text_path ? "true" : "false", t.device_writer ? "device" : "host");
-        }
-    } timing_printer{t_begin};
+    TimingPrinter timing_printer;
     return run_guarded("", [&] {
         KmerCounter kc;
         kc.k(a.k).min_count(a.min_count).format(a.format).input_format(a.input_format).min_quality(a.min_quality).devices(a.devices).sorted(a.sorted);

@@ -47,6 +47,8 @@
 #pragma weak kh_unitigs_links_copy
 // ... and of `clip`
 #pragma weak kh_clip_tips_into
+#pragma weak kh_unitigs_text_begin
+#pragma weak kh_unitigs_text_next
 
 namespace kmerust {
 
@@ -889,19 +891,21 @@ struct Session {
                 check_on(c, kh_result_text_begin(c, f, min_count, nullptr, &nbytes), "kh_result_text_begin");
             }
             Lap lap(timing().write_s);
-            stream_pieces(c, nbytes, out);
+            stream_pieces(c, nbytes, out, kh_result_text_next, "kh_result_text_next");
         }
         if (fflush(out) != 0 || ferror(out))  // (a full disk must not end as a shorter text and exit status 0)
             throw Error(std::string("failed to write the output: ") + std::strerror(errno));
     }
     // Pieces of up to 64 MiB into a few pinned buffers: a second thread fwrite()s piece i while piece i + 1 travels (and the
     // device formats piece i + 2).  A small text takes one pageable buffer: pinning would cost more than the copy.
-    static void stream_pieces(kh_ctx *c, uint64_t nbytes, FILE *out) {
+    // next: kh_result_text_next or kh_unitigs_text_next, `what` its name -- the two streams are pumped the same way.
+    typedef int (*TextNext)(kh_ctx *, uint8_t *, uint64_t, uint64_t *);
+    static void stream_pieces(kh_ctx *c, uint64_t nbytes, FILE *out, TextNext next, const char *next_name) {
         if (nbytes <= (1u << 20)) {
             std::vector<uint8_t> buf((size_t)std::max<uint64_t>(nbytes, 128));
             for (;;) {
                 uint64_t n = 0;
-                check_on(c, kh_result_text_next(c, buf.data(), buf.size(), &n), "kh_result_text_next");
+                check_on(c, next(c, buf.data(), buf.size(), &n), next_name);
                 if (!n || fwrite(buf.data(), 1, (size_t)n, out) != (size_t)n) return;  // (a short write: write_text reports it)
             }
         }
@@ -943,8 +947,8 @@ struct Session {
                 --free_bufs;
             }
             uint64_t n = 0;
-            what = "kh_result_text_next";
-            rc = kh_result_text_next(c, (uint8_t *)bufs[i], piece, &n);
+            what = next_name;
+            rc = next(c, (uint8_t *)bufs[i], piece, &n);
             if (rc != KH_OK || n == 0) break;
             std::lock_guard<std::mutex> lk(mu);
             filled.push_back({i, n});
@@ -1436,6 +1440,30 @@ void write_unitig_summary(FILE *out, const UnitigSummary &u) {
     for (const auto &r : rows) fprintf(out, "%s\t%llu\n", r.first, (unsigned long long)r.second);
 }
 
+// Whether `unitigs -f fasta` / `gfa -f gfa` take their text from the device stream (kh_unitigs_text_*): the library has it (make asan's
+// stub has not), and KMERUST_HOST_FORMAT=1 does not ask for the host writers.
+static bool unitig_text_on_device() {
+    if (!kh_unitigs_text_begin || !kh_unitigs_text_next) return false;
+    const char *e = getenv("KMERUST_HOST_FORMAT");
+    return !(e && e[0] && e[0] != '0');
+}
+// The live unitigs of c as text from the device: sized (result_s), then pumped to `out` as the count command's text is (write_s).
+static void write_unitig_text(kh_ctx *c, uint32_t format, FILE *out) {
+    timing().device_writer = true;
+    uint64_t nbytes = 0;
+    {
+        Lap lap(timing().result_s);
+        Session::check_on(c, kh_unitigs_text_begin(c, format, &nbytes), "kh_unitigs_text_begin");
+    }
+    {
+        Lap lap(timing().write_s);
+        Session::stream_pieces(c, nbytes, out, kh_unitigs_text_next, "kh_unitigs_text_next");
+    }
+    Session::check_on(c, kh_unitigs_end(c), "kh_unitigs_end");
+    if (fflush(out) != 0 || ferror(out))  // (a full disk must not end as a shorter text and exit status 0)
+        throw Error(std::string("failed to write the output: ") + std::strerror(errno));
+}
+
 void unitigs_index(const std::string &index, uint64_t min_count, UnitigFormat fmt, FILE *out) {
     if (!kh_unitigs_begin || !kh_unitigs_copy || !kh_unitigs_copy_device || !kh_unitigs_end || !kh_merge_pairs)
         throw Error("unitigs needs a kmerhip library with kh_unitigs_begin, kh_unitigs_copy, kh_unitigs_end and kh_merge_pairs; the one this program was built against has neither");
@@ -1444,7 +1472,12 @@ void unitigs_index(const std::string &index, uint64_t min_count, UnitigFormat fm
     IndexTable t(idx, -1);
     idx = PackedCounts();  // (the host copy is no longer needed)
     uint64_t nu = 0, nb = 0;
-    Session::check_on(t.c, kh_unitigs_begin(t.c, min_count, &nu, &nb), "kh_unitigs_begin");
+    {
+        Lap lap(timing().result_s);
+        Session::check_on(t.c, kh_unitigs_begin(t.c, min_count, &nu, &nb), "kh_unitigs_begin");
+    }
+    if (fmt == UnitigFormat::Fasta && unitig_text_on_device()) return write_unitig_text(t.c, KH_UNI_TEXT_FASTA, out);  // (no row, no base crosses the link)
+    Lap lap(timing().write_s);
     std::vector<uint64_t> rows(nu * KH_UNI_WORDS);
     std::vector<uint8_t> bases(fmt == UnitigFormat::Fasta ? nb : 0);
     Session::check_on(t.c, kh_unitigs_copy(t.c, nu ? rows.data() : nullptr, nu ? nu : 0, bases.empty() ? nullptr : bases.data(), bases.size()), "kh_unitigs_copy");
@@ -1484,7 +1517,12 @@ void gfa_index(const std::string &index, uint64_t min_count, GfaFormat fmt, FILE
     IndexTable t(idx, -1);
     idx = PackedCounts();  // (the host copy is no longer needed)
     uint64_t nu = 0, nb = 0, nl = 0;
-    Session::check_on(t.c, kh_unitigs_begin_linked(t.c, min_count, &nu, &nb, &nl), "kh_unitigs_begin_linked");
+    {
+        Lap lap(timing().result_s);
+        Session::check_on(t.c, kh_unitigs_begin_linked(t.c, min_count, &nu, &nb, &nl), "kh_unitigs_begin_linked");
+    }
+    if (fmt == GfaFormat::Gfa && unitig_text_on_device()) return write_unitig_text(t.c, KH_UNI_TEXT_GFA, out);  // (no row, base or link word crosses the link)
+    Lap lap(timing().write_s);
     std::vector<uint64_t> rows(nu * KH_UNI_WORDS), links(nl);
     std::vector<uint8_t> bases(fmt == GfaFormat::Gfa ? nb : 0);
     Session::check_on(t.c, kh_unitigs_copy(t.c, nu ? rows.data() : nullptr, nu ? nu : 0, bases.empty() ? nullptr : bases.data(), bases.size()), "kh_unitigs_copy");

@@ -358,8 +358,9 @@ enum class UnitigFormat { Fasta, Summary };
 // "{name}\t{value}" lines: unitigs, kmers, bases, circular, longest, n50.
 void write_unitig_summary(FILE *out, const UnitigSummary &u);
 // The index into a device table (as `graph` loads one), kh_unitigs_begin / kh_unitigs_copy / kh_unitigs_end; Fasta: unitig_header and
-// the unitig's bases, one record each; Summary: unitig_summary of the rows.  Throws Error -- also against a library without the four
-// kh_unitigs_* entry points.
+// the unitig's bases, one record each -- the same bytes formatted on the device and streamed out (kh_unitigs_text_*) where the library
+// has those calls and KMERUST_HOST_FORMAT=1 is not set; Summary: unitig_summary of the rows.  Throws Error -- also against a library
+// without the four kh_unitigs_* entry points.
 void unitigs_index(const std::string &index, uint64_t min_count, UnitigFormat fmt, FILE *out);
 
 // ---- the unitig graph of an index as GFA (`kmerust gfa`; no reference counterpart) ------------------------------------------------------
@@ -414,7 +415,8 @@ enum class GfaFormat { Gfa, Summary };
 // "{name}\t{value}" lines: unitigs, links, self_links, dead_ends, isolated, tips.
 void write_link_summary(FILE *out, const LinkSummary &s);
 // The index into a device table (as `unitigs` loads one), kh_unitigs_begin_linked / kh_unitigs_copy / kh_unitigs_links_copy /
-// kh_unitigs_end; Gfa: the header line, one S line per unitig, one L line per link in link order; Summary: link_summary.  Throws
+// kh_unitigs_end; Gfa: the header line, one S line per unitig, one L line per link in link order (from the device's kh_unitigs_text_*
+// stream, or by the writers above under KMERUST_HOST_FORMAT=1 / against a library without it); Summary: link_summary.  Throws
 // Error -- also against a library without the kh_unitigs_begin_linked / kh_unitigs_links_copy entry points.
 void gfa_index(const std::string &index, uint64_t min_count, GfaFormat fmt, FILE *out);
 

@@ -53,6 +53,10 @@ def GRAPH_LEFT(c):
 # KH_UNI_*: the words of a unitig row (kh_unitigs_*)
 UNI_WORDS, UNI_START, UNI_KMERS, UNI_COUNT_SUM, UNI_FLAGS = 4, 0, 1, 2, 3
 UNI_CIRCULAR = 1
+# KH_UNI_TEXT_*: the formats of kh_unitigs_text_begin; UNI_TEXT_TILE: the bytes of the document one workgroup formats (UT_TILE of
+# krust_amd/csrc/unitig_text.hip.h) -- the tests place records on its edges
+KH_UNI_TEXT_FASTA, KH_UNI_TEXT_GFA = 1, 2
+UNI_TEXT_TILE = 8192
 
 
 # KH_UNI_LINK_*: a link word of kh_unitigs_links_* -- 2 * from_unitig + from_sign above 2 * to_unitig + to_sign, + = 0, - = 1
@@ -169,6 +173,9 @@ SYMBOLS = {
     "kh_unitigs_begin_linked": (C.c_int, [_P, _U64, _P, _P, _P]),
     "kh_unitigs_links_copy_device": (C.c_int, [_P, _P, _U64]),
     "kh_unitigs_links_copy": (C.c_int, [_P, _P, _U64]),
+    "kh_unitigs_text_begin": (C.c_int, [_P, C.c_uint32, C.POINTER(_U64)]),
+    "kh_unitigs_text_next": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
+    "kh_unitigs_text_next_device": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
     "kh_clip_tips_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_pop_bubbles_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
@@ -607,6 +614,52 @@ class DeviceCounter:
             return self.unitigs_copy(nu, nb)
         finally:
             self.unitigs_end()
+
+    # -- the live unitigs as text, formatted on the device --------------------
+    def unitigs_text_begin(self, format):
+        """kh_unitigs_text_begin: starts (or restarts) the text stream of the live unitigs; format: "fasta" (what `kmerust unitigs`
+        prints) | "gfa" (what `kmerust gfa` prints; needs unitigs_begin_linked) or a KH_UNI_TEXT_* value.  Returns the document's
+        length in bytes."""
+        nb = _U64(0)
+        fmt = {"fasta": KH_UNI_TEXT_FASTA, "gfa": KH_UNI_TEXT_GFA}.get(format, format)
+        self._check(lib().kh_unitigs_text_begin(self._h, int(fmt), C.byref(nb)))
+        return int(nb.value)
+
+    def unitigs_text_next(self, buf, cap=None):
+        """The next piece -- a byte range, min(cap, bytes left) long -- into `buf`: a writable numpy uint8 array (pageable, or a
+        PinnedArray's) or an integer host address with `cap`.  Returns the bytes written; 0 = the stream has ended."""
+        if isinstance(buf, np.ndarray):
+            assert buf.dtype == np.uint8 and buf.flags.c_contiguous and buf.flags.writeable
+            addr, cap = buf.ctypes.data, buf.size if cap is None else min(int(cap), buf.size)
+        else:
+            addr, cap = int(buf), int(cap)
+        n = _U64(0)
+        self._check(lib().kh_unitigs_text_next(self._h, addr, cap, C.byref(n)))
+        return int(n.value)
+
+    def unitigs_text_next_device(self, out, cap=None):
+        """The next piece into DEVICE memory at any alignment: `out` is a uint8 tensor on this context's device, or an integer
+        device address with `cap`.  Returns the bytes written; 0 = the stream has ended."""
+        if isinstance(out, int):
+            addr, cap = out, int(cap)
+        else:
+            addr, cap = out.data_ptr(), out.numel() * out.element_size() if cap is None else int(cap)
+        n = _U64(0)
+        self._check(lib().kh_unitigs_text_next_device(self._h, addr, cap, C.byref(n)))
+        return int(n.value)
+
+    def unitigs_text(self, format, piece_bytes=8 << 20):
+        """The whole document of the live unitigs as `bytes`: begin, then pieces of piece_bytes until the stream has ended."""
+        total = self.unitigs_text_begin(format)
+        buf = np.empty(max(int(piece_bytes), 1), dtype=np.uint8)
+        out = bytearray()
+        while True:
+            n = self.unitigs_text_next(buf)
+            if n == 0:
+                break
+            out += buf[:n].tobytes()
+        assert len(out) == total, (len(out), total)
+        return bytes(out)
 
     # -- links between unitigs: the edges of the compacted graph -------------
     def unitigs_begin_linked(self, min_count=1):

@@ -22,6 +22,14 @@ With --pop, per size and in one process, these three, on the same table:
   clip_tips_into       kh_clip_tips_into(1, max_kmers = k), as with --clip
   pop_bubbles_into     kh_pop_bubbles_into(1, max_kmers = 2 k) into the same fresh context, kh_reset (not timed) before every call;
                        pop_share = the part of its median that is not unitigs_begin_linked's; the nine words beside it
+With --text, in ONE PROCESS PER SIZE, the GFA text of the unitigs formatted on the device (kh_unitigs_text_*), on the same table:
+  unitigs_begin_linked kh_unitigs_begin_linked(1), as above
+  text_begin           kh_unitigs_text_begin(gfa): a length per record and per link line, two scans; n_bytes beside it
+  text_drain_device    every kh_unitigs_text_next_device into one 64 MiB device buffer, then a device synchronise -- also as bytes / s;
+                       text_share = (text_begin + text_drain_device) / unitigs_begin_linked
+  text_drain_pinned    every kh_unitigs_text_next into three pinned 64 MiB buffers in turn -- also as bytes / s
+  copies_pinned        the yardstick for the link: kh_unitigs_copy + kh_unitigs_links_copy of the same unitigs into pinned arrays, as
+                       bytes / s of what they move (32 B per unitig, 1 per base, 8 per link)
 The measurement runs in a child process with a timeout; a failure is reported as {"error": ...}."""
 import argparse
 import json
@@ -159,7 +167,87 @@ def measure_clip_one(n, k, pop=False):
     return out
 
 
+def measure_text_one(n, k):
+    import ctypes as C
+    import numpy as np
+    import torch
+    from krust_amd import native
+    rl = 150
+    t = torch.empty(n * (rl + 1), dtype=torch.uint8, device="cuda:0")
+    native.synth_reads_device(t.data_ptr(), None, 20260130, 1 << 28, rl, 0, n, device=0)
+    torch.cuda.synchronize()
+    a = native.DeviceCounter(k, device=0)
+    a.push_device(t.data_ptr(), None, t.numel())
+    st = a.finish()
+    del t
+    out = {"k": k, "reads": n, "table": {f: st[f] for f in ("distinct", "kmers", "table_slots", "slot_bytes")}}
+    nodes = st["distinct"]
+    linked = timed(lambda: a.unitigs_begin_linked(1))
+    nu, nb, nl = a.unitigs_begin_linked(1)
+    out.update(nodes=nodes, unitigs=nu, bases=nb, n_links=nl)
+    out["unitigs_begin_linked"] = dict(linked, nodes_per_s=nodes / linked["median_s"])
+    out["text_begin"] = timed(lambda: a.unitigs_text_begin("gfa"))
+    total = a.unitigs_text_begin("gfa")
+    out["n_bytes"] = total
+    piece = 64 << 20
+    d_buf = torch.empty(piece, dtype=torch.uint8, device="cuda:0")
+    pins = [native.PinnedArray(piece) for _ in range(3)]
+
+    def timed_drain(next_piece):
+        ts = []
+        for rep in range(6):                  # one warm drain, then five; the begin in front of each is not timed
+            assert a.unitigs_text_begin("gfa") == total
+            torch.cuda.synchronize()
+            got, i = 0, 0
+            t0 = time.perf_counter()
+            while True:
+                m = next_piece(i)
+                if m == 0:
+                    break
+                got += m
+                i += 1
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+            assert got == total
+        ts = sorted(ts[1:])
+        r = {"median_s": ts[len(ts) // 2], "spread_s": ts[-1] - ts[0]}
+        return dict(r, bytes_per_s=total / r["median_s"])
+
+    out["text_drain_device"] = timed_drain(lambda i: a.unitigs_text_next_device(d_buf))
+    heads = []
+
+    def next_pinned(i):
+        m = a.unitigs_text_next(pins[i % 3].array)
+        if i == 0:
+            heads.append(bytes(pins[0].array[:11]))
+        return m
+
+    out["text_drain_pinned"] = timed_drain(next_pinned)
+    out["text_share"] = (out["text_begin"]["median_s"] + out["text_drain_device"]["median_s"]) / linked["median_s"]
+    assert len(heads) == 6 and set(heads) == {b"H\tVN:Z:1.0\n"}, heads
+    for p in pins:
+        p.close()
+    rows = native.PinnedArray(max(4 * nu, 1), np.uint64)
+    bases = native.PinnedArray(max(nb, 1))
+    links = native.PinnedArray(max(nl, 1), np.uint64)
+    L = native.lib()
+
+    def copies():
+        assert L.kh_unitigs_copy(a._h, rows.array.ctypes.data, nu, bases.array.ctypes.data, nb) == 0
+        assert L.kh_unitigs_links_copy(a._h, links.array.ctypes.data, nl) == 0
+
+    moved = 32 * nu + nb + 8 * nl
+    c = timed(copies)
+    out["copies_pinned"] = dict(c, bytes=moved, bytes_per_s=moved / c["median_s"])
+    a.unitigs_end()
+    a.close()
+    return out
+
+
 def measure(args):
+    if args.text:
+        print("RESULT " + json.dumps([measure_text_one(n, args.k) for n in args.reads]))
+        return
     one = (lambda n, k: measure_clip_one(n, k, pop=True)) if args.pop else measure_clip_one if args.clip else measure_one
     print("RESULT " + json.dumps([one(n, args.k) for n in args.reads]))
 
@@ -171,10 +259,27 @@ def main():
     ap.add_argument("--timeout", type=int, default=900)
     ap.add_argument("--clip", action="store_true", help="kh_clip_tips_into beside kh_unitigs_begin_linked, nothing else")
     ap.add_argument("--pop", action="store_true", help="kh_pop_bubbles_into beside kh_clip_tips_into and kh_unitigs_begin_linked, nothing else")
+    ap.add_argument("--text", action="store_true", help="kh_unitigs_text_* beside kh_unitigs_begin_linked and the copies, one process per size")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
         measure(args)
+        return
+    if args.text:   # one process per size
+        res = []
+        for n in args.reads:
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--text", "--k", str(args.k), "--reads", str(n)]
+            try:
+                p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
+                line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
+                if p.returncode != 0 or not line:
+                    res.append({"reads": n, "error": f"exit {p.returncode}", "stderr": p.stderr[-2000:]})
+                    break   # (nothing more is started on a device that may have faulted)
+                res += json.loads(line[-1][7:])
+            except subprocess.TimeoutExpired:
+                res.append({"reads": n, "error": f"no result within {args.timeout} s"})
+                break
+        print(json.dumps({"probe": "unitig-text", "result": res}, indent=1))
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k)] + (["--clip"] if args.clip else []) + (["--pop"] if args.pop else []) + ["--reads"] + [str(n) for n in args.reads]
     try:
