@@ -131,6 +131,9 @@ pub mod sys {
         pub fn kh_unitigs_text_begin(ctx: *mut KhCtx, format: u32, n_bytes: *mut u64) -> c_int;
         pub fn kh_unitigs_text_next(ctx: *mut KhCtx, buf: *mut u8, cap: u64, n: *mut u64) -> c_int;
         pub fn kh_unitigs_text_next_device(ctx: *mut KhCtx, d_buf: *mut u8, cap: u64, n: *mut u64) -> c_int;
+        /// `out[i]` = where on the live unitigs the k-mer at window start i lies: 2 * unitig + sign above the offset, or a special
+        pub fn kh_unitigs_locate_device(ctx: *mut KhCtx, d_bases: *const u8, d_qual: *const u8, n: u64, d_out: *mut u64) -> c_int;
+        pub fn kh_unitigs_locate(ctx: *mut KhCtx, bases: *const u8, qual: *const u8, n: u64, out: *mut u64) -> c_int;
         /// one round of tip clipping of `src`'s compacted graph at `min_count`: the k-mers of the surviving unitigs are added to `dst`
         /// (`count[key] += c`); `out` takes the 8 words KH_CLIP_* of the header names
         pub fn kh_clip_tips_into(dst: *mut KhCtx, src: *mut KhCtx, min_count: u64, max_kmers: u64, out: *mut u64) -> c_int;
@@ -234,6 +237,18 @@ pub const UNI_CIRCULAR: u64 = 1;
 /// `KH_UNI_TEXT_FASTA` / `KH_UNI_TEXT_GFA`: the formats of [`HipKmerMap::unitigs_text`].
 pub const UNI_TEXT_FASTA: u32 = 1;
 pub const UNI_TEXT_GFA: u32 = 2;
+/// `KH_LOC_NO_WINDOW`: a word of [`HipKmerMap::unitigs_locate`] where [`HipKmerMap::profile`] says [`PROFILE_NO_WINDOW`].
+pub const LOC_NO_WINDOW: u64 = !0u64;
+/// `KH_LOC_ABSENT`: a valid window whose k-mer is no node of the located unitigs.
+pub const LOC_ABSENT: u64 = !0u64 - 1;
+/// `KH_LOC_IS_PLACE(w)`: neither of the two specials.
+pub const fn loc_is_place(w: u64) -> bool { w < LOC_ABSENT }
+/// `KH_LOC_UNITIG(w)`: the unitig (a row index of `kh_unitigs_copy`) the window's k-mer lies in.
+pub const fn loc_unitig(w: u64) -> u32 { (w >> 33) as u32 }
+/// `KH_LOC_SIGN(w)`: 0 = the window reads the k-mer as the unitig's reported sequence spells it, 1 = as its reverse complement.
+pub const fn loc_sign(w: u64) -> u32 { ((w >> 32) & 1) as u32 }
+/// `KH_LOC_OFFSET(w)`: the k-mer is bases offset .. offset + k of the unitig's reported sequence.
+pub const fn loc_offset(w: u64) -> u32 { (w & 0xFFFF_FFFF) as u32 }
 /// `KH_UNI_LINK_FROM(w)`: the unitig a link word of `kh_unitigs_links_copy` leaves (a row index of `kh_unitigs_copy`).
 pub const fn uni_link_from(w: u64) -> u32 { (w >> 33) as u32 }
 /// `KH_UNI_LINK_FROM_SIGN(w)`: 0 = it leaves the right end of the reported sequence (+), 1 = that of its reverse complement (-).
@@ -647,6 +662,29 @@ impl HipKmerMap {
         check(self.ctx, end)?;
         text.truncate(at);
         Ok(text)
+    }
+
+    /// The windows of `bases` located on the unitigs of the table at `min_count` (`kh_unitigs_begin_linked` / `kh_unitigs_locate` /
+    /// `kh_unitigs_end`): one word per byte of the flat buffer (records separated by a byte outside ACGTacgt; `qual` masks as in
+    /// counting) -- [`LOC_NO_WINDOW`], [`LOC_ABSENT`], or a place that [`loc_unitig`], [`loc_sign`] and [`loc_offset`] take apart.
+    /// The unitig indices are the row indices of [`unitigs_linked`](Self::unitigs_linked) at the same `min_count`.
+    pub fn unitigs_locate(&self, min_count: u64, bases: &[u8], qual: Option<&[u8]>) -> Result<Vec<u64>, HipError> {
+        if let Some(q) = qual {
+            if q.len() != bases.len() {
+                return Err(HipError::Device("qual must have the same length as bases".into()));
+            }
+        }
+        let (mut nu, mut nb, mut nl) = (0u64, 0u64, 0u64);
+        check(self.ctx, unsafe { sys::kh_unitigs_begin_linked(self.ctx, min_count, &mut nu, &mut nb, &mut nl) })?;
+        let mut out = vec![0u64; bases.len()];
+        let rc = unsafe {
+            sys::kh_unitigs_locate(self.ctx, bases.as_ptr(), qual.map_or(std::ptr::null(), |q| q.as_ptr()), bases.len() as u64, out.as_mut_ptr())
+        };
+        let err = check(self.ctx, rc);  // (before kh_unitigs_end replaces the error text)
+        let end = unsafe { sys::kh_unitigs_end(self.ctx) };
+        err?;
+        check(self.ctx, end)?;
+        Ok(out)
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

@@ -536,6 +536,44 @@ int kh_unitigs_text_begin(kh_ctx *ctx, uint32_t format, uint64_t *n_bytes /* may
 int kh_unitigs_text_next(kh_ctx *ctx, uint8_t *buf, uint64_t cap, uint64_t *n);
 int kh_unitigs_text_next_device(kh_ctx *ctx, uint8_t *d_buf, uint64_t cap, uint64_t *n);
 
+/* ---- the k-mers of new sequences LOCATED on the live unitigs (what read threading and pseudo-alignment start from) -------- */
+/* kh_profile* tell a window the COUNT of its k-mer; these tell it WHERE in the compacted graph that k-mer is.  They need the live
+ * unitigs of kh_unitigs_begin or kh_unitigs_begin_linked.  Let Q_u be the reported sequence of unitig u (row index u, L_u = KMERS).
+ * INPUT, windows, quality masking and the chunks of the host form are those of kh_profile_device / kh_profile: a flat buffer,
+ *   separators outside ACGTacgt, d_bases and d_qual at any alignment.
+ * OUTPUT: n words, indexed by the window start; every one is written.
+ *   - KH_LOC_NO_WINDOW exactly where kh_profile writes KH_PROFILE_NO_WINDOW.
+ *   - KH_LOC_ABSENT: a valid window whose canonical k-mer is not in S -- not in the table, or with a count below the min_count
+ *     of the begin that built the unitigs.
+ *   - otherwise a PLACE.  With w the window's k letters there is exactly one (u, j), 0 <= j < L_u, with Q_u[j .. j+k) == w or
+ *     Q_u[j .. j+k) == rc(w): every node lies in exactly one unitig exactly once (a circular unitig has L + k - 1 bases too, so
+ *     all its L k-mers are windows of its bases).  Sign 0 (+): Q_u[j .. j+k) == w; sign 1 (-): it equals rc(w); a palindromic w
+ *     (even k) is +.  High 32 bits = 2 * u + sign -- the state encoding of a link word's halves, so a located window and a
+ *     link end compare directly --, low 32 bits = j.  u <= 2^31 - 2, so the high word of a place is never that of the specials.
+ * WHAT FOLLOWS for two consecutive window starts i, i + 1 that are both places: either both lie in the same unitig with the
+ *   same sign and the offset moves by +1 (+) or by -1 (-); or window i is at the last offset of its direction (L - 1 for +, 0
+ *   for -), window i + 1 at the first offset of its direction (0 for +, L - 1 for -) and (2u + s) -> (2u' + s') is a link word
+ *   of kh_unitigs_begin_linked -- the closing link of a circular unitig is such a link.  A read is a walk in the GFA.
+ *   REVERSE COMPLEMENT: for a record R of m valid bases, locate(rc(R))[i] is locate(R)[m - k - i] with the sign flipped (a
+ *   palindrome is + both times).
+ * ENTRY: both enter as readers, like kh_profile*: the table is read in the form it is in, kh_stats is unchanged, a
+ *   kh_result_text_* or kh_unitigs_text_* stream goes on, and they may come between any two readers.  KH_ERR_STATE without live
+ *   unitigs; KH_ERR_BAD_ARG for a NULL array with n > 0 or an output that is not 8-byte aligned (the context stays usable);
+ *   n == 0 is KH_OK; an empty S (0 unitigs) gives only the two specials.
+ * THE INDEX: the first locate call after a begin builds the place map, one uint64 per table slot (table_slots * 8 bytes of
+ *   device memory of the context's own), from the rows and bases.  It lives and dies with the unitigs: kh_unitigs_end, the next
+ *   begin, kh_reset, kh_destroy; a begin that is never located allocates nothing for it.  KH_ERR_OOM follows the rule of the
+ *   reading calls: the context is not poisoned, the unitigs stay live, nothing of the index stays allocated, and the next
+ *   locate call tries again.  Later calls of kh_unitigs_locate_device allocate nothing. */
+#define KH_LOC_NO_WINDOW (~0ull)
+#define KH_LOC_ABSENT (~0ull - 1ull)
+#define KH_LOC_IS_PLACE(w) ((uint64_t)(w) < KH_LOC_ABSENT)
+#define KH_LOC_UNITIG(w) ((uint32_t)((uint64_t)(w) >> 33))
+#define KH_LOC_SIGN(w) ((uint32_t)(((uint64_t)(w) >> 32) & 1u))
+#define KH_LOC_OFFSET(w) ((uint32_t)((uint64_t)(w) & 0xFFFFFFFFu))
+int kh_unitigs_locate_device(kh_ctx *ctx, const uint8_t *d_bases, const uint8_t *d_qual, uint64_t n, uint64_t *d_out);
+int kh_unitigs_locate(kh_ctx *ctx, const uint8_t *bases, const uint8_t *qual, uint64_t n, uint64_t *out);
+
 /* ---- tip clipping: one round of removing short dead-end branches (what assemblers do first with the compacted graph) --- */
 /* Take the unitigs and links of kh_unitigs_begin_linked(src, min_count): rows, end states (i, +) and (i, -) and link words exactly
  * as defined above.  out(i, s) is the set of links whose from-state is (i, s).

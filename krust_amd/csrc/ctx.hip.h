@@ -387,6 +387,7 @@ struct kh_ctx {
     uint8_t *pf_d[2] = {nullptr, nullptr};
     uint8_t *pf_h[2] = {nullptr, nullptr};
     u64 pf_chunk = 0;
+    u64 pf_out_bytes = 0;  // bytes per window start of the buffers' last part: 4 (kh_profile) or 8 (kh_unitigs_locate)
     hipEvent_t pf_in[2] = {nullptr, nullptr}, pf_run[2] = {nullptr, nullptr}, pf_out[2] = {nullptr, nullptr};
     // kh_profile_records: the rows (KH_REC_WORDS words per record) and the record offsets, on the device for the whole call
     uint32_t *pr_rows = nullptr;  u64 pr_rows_cap = 0;  // records
@@ -405,6 +406,9 @@ struct kh_ctx {
         bool linked = false;      // built by kh_unitigs_begin_linked: the link words, one per (end state, successor)
         u64 *links = nullptr;     // (nullptr when there are none)
         u64 n_links = 0;
+        // kh_unitigs_locate* (locate.hip): the place map, one word per table slot -- (2 u + o) << 32 | j for the node in that slot, all ones
+        // for a slot that holds no node of S.  Built by the first locate call after a begin (cap * 8 bytes), released by unitigs_release().
+        u64 *where = nullptr;
         // kh_unitigs_text_* (unitig_text.hip): these unitigs as text.  begin sizes every record and link line and scans both; next formats
         // ranges of whole tiles of UT_TILE bytes into one of two device chunks of the stream's OWN -- never the partition buffers: a
         // kh_result_text_* stream may run beside it -- and hands their bytes out: chunk i + 1 is formatted on `stream` while chunk i
@@ -483,6 +487,9 @@ struct Entry {
     bool narrow_ok = false;     // the 8-byte image stays what it is (false: widened into the 16-byte table first)
     bool reader = false;        // the call only reads the table: a text stream in progress and the unitigs of kh_unitigs_begin survive it
 };
+// Slot indices are stable for as long as un.live holds: only `reader` entries keep it, and both reader presets below set narrow_ok,
+// so that enter() neither widens the image nor moves, grows or clears a table that holds counts (nothing is pending behind live
+// unitigs: a push is no reader).  The place map of kh_unitigs_locate* (Unitigs::where) is indexed by slot and relies on it.
 // The pair and dense merges, the exports by owner, kh_comm_init, the dst of kh_combine_into / kh_clip_tips_into / kh_pop_bubbles_into: a cleared
 // 16-byte table, everything pending counted, whatever hangs on the table's content (text stream, unitigs, merge window) ended.
 constexpr Entry ENTER_WRITE{};
@@ -591,6 +598,15 @@ inline unsigned uni_grid(u64 items) { return (unsigned)grid_for(items); }  // ev
 void unitigs_text_release(kh_ctx *c);  // the offsets, chunks and events of a kh_unitigs_text_* stream (unitigs_release calls it)
 // ---- profile.hip
 void profile_release(kh_ctx *c);  // kh_destroy: the chunk buffers and events of kh_profile, the rows of kh_profile_records
+// The chunks of a host form that streams a flat buffer through the device (kh_profile, kh_profile_records, kh_unitigs_locate):
+// window starts per chunk, sized from the call (KMERHIP_PROFILE_CHUNK_KB in the test build), and the two device buffers
+// [bases | qualities | out_bytes per window start] with their pinned twins and events.  who: the call, for the error text.
+constexpr u64 PF_PAD = 64;  // behind a chunk's bases: its k - 1 bytes of the next chunk, and the kernel's 16-byte loads
+inline u64 pf_in_stride(u64 chunk) { return (chunk + PF_PAD + 15) & ~15ull; }
+u64 profile_chunk(const kh_ctx *c, u64 n);
+int profile_buffers(kh_ctx *c, u64 chunk, u64 out_bytes = 4, const char *who = "kh_profile: chunk buffers");
+// ---- locate.hip
+// (the place map is released by unitigs_release(): it is memory of the unitigs)
 
 // ---- stage timing: HIP events on the launch stream, resolved lazily ---------------------------
 struct StageTimer {

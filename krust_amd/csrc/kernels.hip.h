@@ -435,6 +435,25 @@ struct Roller {
         key = fwd < rc ? fwd : rc;  // integer min == the reference's lexicographic choice (kmer.rs:348-365)
         return (good >> (15 - j)) & 1u;
     }
+
+    // next() that also says which strand the window is read on: strand = 1 when the canonical key is the reverse complement
+    // of the window's letters, 0 when it is the letters themselves (a palindrome: 0).  (locate_kernel; the kernels that
+    // count or profile keep next() and compile to what they did.)
+    __device__ __forceinline__ bool next(int j, u64 &key, uint32_t &strand) {
+        const uint32_t c = (code >> (30 - 2 * j)) & 3u;
+        fhi = __builtin_amdgcn_alignbit(fhi, flo, 30);
+        flo = (flo << 2) | c;
+        rlo = __builtin_amdgcn_alignbit(rhi, rlo, 2);
+        rhi >>= 2;
+        const uint32_t ins = (c ^ 3u) << ins_sh;
+        rlo |= ins & ins_mlo;
+        rhi |= ins & ins_mhi;
+        const u64 fwd = ((u64)(fhi & kmhi) << 32) | (flo & kmlo);
+        const u64 rc = ((u64)rhi << 32) | rlo;
+        strand = fwd > rc ? 1u : 0u;
+        key = strand ? rc : fwd;
+        return (good >> (15 - j)) & 1u;
+    }
 };
 
 template <bool QUAL>

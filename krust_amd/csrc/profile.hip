@@ -345,7 +345,6 @@ namespace khi {
 
 constexpr u64 PF_CHUNK_MAX = 4ull << 20;   // window starts per chunk of kh_profile: 4 MiB of bases in, 16 MiB of profile out
 constexpr u64 PF_CHUNK_MIN = 64ull << 10;
-constexpr u64 PF_PAD = 64;                 // behind a chunk's bases: its k - 1 bytes of the next chunk, and the kernel's 16-byte loads
 
 // the chunk buffers and events of the two host forms (profile_buffers grows them by releasing them first)
 static void chunk_release(kh_ctx *c) {
@@ -360,6 +359,7 @@ static void chunk_release(kh_ctx *c) {
         }
     }
     c->pf_chunk = 0;
+    c->pf_out_bytes = 0;
 }
 
 void profile_release(kh_ctx *c) {
@@ -371,9 +371,48 @@ void profile_release(kh_ctx *c) {
     c->pr_rows_cap = c->pr_rec_cap = 0;
 }
 
-namespace {
+// Window starts per chunk of a host form over n bytes.
+u64 profile_chunk(const kh_ctx *c, u64 n) {
+    u64 chunk = PF_CHUNK_MIN;
+    while (chunk < n && chunk < PF_CHUNK_MAX) chunk *= 2;
+#if KH_TESTING
+    if (c->knobs.profile_chunk_kb) chunk = c->knobs.profile_chunk_kb << 10;  // (tests: chunk edges inside reads and records)
+#endif
+    return chunk;
+}
 
-u64 pf_in_stride(u64 chunk) { return (chunk + PF_PAD + 15) & ~15ull; }
+// The two chunk buffers on the device ([bases | qualities | out_bytes per window start]) and their pinned twins, for `chunk` window
+// starts each.  Buffers that are too small in either measure are released and allocated again for the larger of both.
+int profile_buffers(kh_ctx *c, u64 chunk, u64 out_bytes, const char *who) {
+    if (!c->cstream) HIP_TRY(c, hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
+    if (!c->cstream2) HIP_TRY(c, hipStreamCreateWithFlags(&c->cstream2, hipStreamNonBlocking));
+    if (c->pf_chunk < chunk || c->pf_out_bytes < out_bytes) {
+        chunk = std::max(chunk, c->pf_chunk);
+        out_bytes = std::max(out_bytes, c->pf_out_bytes);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        chunk_release(c);
+        const u64 bytes = 2 * pf_in_stride(chunk) + out_bytes * chunk;
+        for (int i = 0; i < 2; ++i) {
+            hipError_t e = dev_malloc((void **)&c->pf_d[i], bytes);
+            if (e == hipSuccess) e = pin_malloc((void **)&c->pf_h[i], bytes, hipHostMallocDefault);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                chunk_release(c);
+                return soft_oom(c, who, e);  // (a reading call: the context stays usable)
+            }
+        }
+        c->pf_chunk = chunk;
+        c->pf_out_bytes = out_bytes;
+    }
+    for (int i = 0; i < 2; ++i) {
+        hipEvent_t *ev[] = {&c->pf_in[i], &c->pf_run[i], &c->pf_out[i]};
+        for (hipEvent_t *e : ev)
+            if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    return KH_OK;
+}
+
+namespace {
 
 // What profile_records_kernel needs beyond profile_kernel's arguments (see there).
 struct RecArgs {
@@ -424,33 +463,6 @@ int profile_range(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 
                                (const uint8_t *)nullptr, 0, vbeg, vend, ntiles, tpb, c->k, 0u, tab, d_out, nout);
     });
     HIP_TRY(c, hipGetLastError());
-    return KH_OK;
-}
-
-// The two chunk buffers on the device ([bases | qualities | profile]) and their pinned twins, for `chunk` window starts each.
-int profile_buffers(kh_ctx *c, u64 chunk) {
-    if (!c->cstream) HIP_TRY(c, hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
-    if (!c->cstream2) HIP_TRY(c, hipStreamCreateWithFlags(&c->cstream2, hipStreamNonBlocking));
-    if (c->pf_chunk < chunk) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        chunk_release(c);
-        const u64 bytes = 2 * pf_in_stride(chunk) + 4 * chunk;
-        for (int i = 0; i < 2; ++i) {
-            hipError_t e = dev_malloc((void **)&c->pf_d[i], bytes);
-            if (e == hipSuccess) e = pin_malloc((void **)&c->pf_h[i], bytes, hipHostMallocDefault);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                chunk_release(c);
-                return soft_oom(c, "kh_profile: chunk buffers", e);  // (a reading call: the context stays usable)
-            }
-        }
-        c->pf_chunk = chunk;
-    }
-    for (int i = 0; i < 2; ++i) {
-        hipEvent_t *ev[] = {&c->pf_in[i], &c->pf_run[i], &c->pf_out[i]};
-        for (hipEvent_t *e : ev)
-            if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
     return KH_OK;
 }
 
@@ -514,11 +526,7 @@ extern "C" int kh_profile(kh_ctx *c, const uint8_t *bases, const uint8_t *qual, 
     if (rc != KH_OK) return rc;
     if (n == 0) return KH_OK;
     const bool with_qual = qual != nullptr && c->minq >= 0;
-    u64 chunk = PF_CHUNK_MIN;
-    while (chunk < n && chunk < PF_CHUNK_MAX) chunk *= 2;
-#if KH_TESTING
-    if (c->knobs.profile_chunk_kb) chunk = c->knobs.profile_chunk_kb << 10;  // (tests: chunk edges inside reads)
-#endif
+    const u64 chunk = profile_chunk(c, n);
     if ((rc = profile_buffers(c, chunk)) != KH_OK) return rc;
     // pinned / registered caller memory: the copy engine reads and writes it itself, no bounce through pf_h
     const bool in_direct = is_pinned_host(bases) && (!with_qual || is_pinned_host(qual));
@@ -600,11 +608,7 @@ extern "C" int kh_profile_records(kh_ctx *c, const uint8_t *bases, const uint8_t
     if ((rc = records_preset(c, d_rows, nrec, sumw)) != KH_OK) return rc;
     if (n) {
         const bool with_qual = qual != nullptr && c->minq >= 0;
-        u64 chunk = PF_CHUNK_MIN;
-        while (chunk < n && chunk < PF_CHUNK_MAX) chunk *= 2;
-#if KH_TESTING
-        if (c->knobs.profile_chunk_kb) chunk = c->knobs.profile_chunk_kb << 10;  // (tests: chunk edges inside records)
-#endif
+        const u64 chunk = profile_chunk(c, n);
         if ((rc = profile_buffers(c, chunk)) != KH_OK) return rc;
         const bool in_direct = is_pinned_host(bases) && (!with_qual || is_pinned_host(qual));
         const u64 stride = pf_in_stride(c->pf_chunk), k1 = c->k - 1;

@@ -682,6 +682,7 @@ void unitigs_release(kh_ctx *c) {
     if (c->un.rows) (void)dev_free(c->un.rows);  // (synchronises the device)
     if (c->un.bases) (void)dev_free(c->un.bases);
     if (c->un.links) (void)dev_free(c->un.links);
+    if (c->un.where) (void)dev_free(c->un.where);  // (the place map of kh_unitigs_locate*, locate.hip)
     c->un = kh_ctx::Unitigs();
 }
 

@@ -87,6 +87,27 @@ def uni_link_fields(links):
     return hi >> 1, hi & 1, lo >> 1, lo & 1
 
 
+# KH_LOC_*: a word of kh_unitigs_locate* -- 2 * unitig + sign above the offset of the k-mer in that unitig, or one of the two specials
+LOC_NO_WINDOW = 0xFFFFFFFFFFFFFFFF  # KH_LOC_NO_WINDOW: where kh_profile* writes PROFILE_NO_WINDOW
+LOC_ABSENT = 0xFFFFFFFFFFFFFFFE     # KH_LOC_ABSENT: a valid window whose k-mer is not a node of the live unitigs
+
+
+def loc_word(unitig, sign, offset):
+    return ((2 * int(unitig) + int(sign)) << 32) | int(offset)
+
+
+def loc_unpack(words):
+    """The three columns (unitig, sign, offset) of an array of located words, as uint32 arrays, and nothing for the specials:
+    their rows hold whatever the bits say -- mask with loc_is_place() first."""
+    w = np.asarray(words, dtype=np.uint64)
+    hi, lo = (w >> np.uint64(32)).astype(np.uint32), (w & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    return hi >> 1, hi & 1, lo
+
+
+def loc_is_place(words):
+    return np.asarray(words, dtype=np.uint64) < np.uint64(LOC_ABSENT)
+
+
 # KH_CLIP_*: the words of kh_clip_tips_into
 CLIP_WORDS = 8
 CLIP_UNITIGS, CLIP_CANDIDATES, CLIP_CLIPPED, CLIP_CLIPPED_KMERS, CLIP_CLIPPED_COUNT, CLIP_KEPT_KMERS, CLIP_KEPT_COUNT, CLIP_LINKS = range(8)
@@ -176,6 +197,8 @@ SYMBOLS = {
     "kh_unitigs_text_begin": (C.c_int, [_P, C.c_uint32, C.POINTER(_U64)]),
     "kh_unitigs_text_next": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
     "kh_unitigs_text_next_device": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
+    "kh_unitigs_locate_device": (C.c_int, [_P, _P, _P, _U64, _P]),
+    "kh_unitigs_locate": (C.c_int, [_P, _P, _P, _U64, _P]),
     "kh_clip_tips_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_pop_bubbles_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
@@ -689,6 +712,29 @@ class DeviceCounter:
             return rows, bases, self.unitigs_links_copy(nl)
         finally:
             self.unitigs_end()
+
+    # -- new sequences located on the live unitigs -----------------------------
+    def unitigs_locate(self, bases, qual=None, out=None):
+        """kh_unitigs_locate: a uint64 array with one word per byte of the flat buffer `bases` (records separated by a byte outside
+        ACGTacgt; `qual` masks as in counting) -- entry i is LOC_NO_WINDOW where profile() says PROFILE_NO_WINDOW, LOC_ABSENT for a
+        k-mer that is no node of the live unitigs, else the place of the k-mer of bytes i .. i+k-1: loc_unpack() gives unitig, sign
+        and offset.  Needs unitigs_begin / unitigs_begin_linked.  Host memory, pageable or a PinnedArray's; out = a uint64 array to fill."""
+        bp, kb = _addr(bases)
+        n = kb.size if kb is not None else 0
+        qp, kq = _addr(qual)
+        if kq is not None and kq.size != n:
+            raise ValueError("qual must have the same length as bases")
+        if out is None:
+            out = np.empty(n, dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.flags.writeable and out.size >= n
+        self._check(lib().kh_unitigs_locate(self._h, bp, qp, n, out.ctypes.data))
+        return out[:n]
+
+    def unitigs_locate_device(self, d_bases, d_qual, n, d_out):
+        """The same on device memory: integer addresses (e.g. tensor.data_ptr()) of n bases, n quality bytes or None, and n uint64
+        words to fill (8-byte aligned), or torch tensors on this context's device.  Returns when d_out is complete."""
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        self._check(lib().kh_unitigs_locate_device(self._h, ptr(d_bases), ptr(d_qual), int(n), ptr(d_out)))
 
     # -- tip clipping: one round over the compacted graph ---------------------
     def clip_tips_into(self, src, min_count=1, max_kmers=None):

@@ -30,6 +30,13 @@ With --text, in ONE PROCESS PER SIZE, the GFA text of the unitigs formatted on t
   text_drain_pinned    every kh_unitigs_text_next into three pinned 64 MiB buffers in turn -- also as bytes / s
   copies_pinned        the yardstick for the link: kh_unitigs_copy + kh_unitigs_links_copy of the same unitigs into pinned arrays, as
                        bytes / s of what they move (32 B per unitig, 1 per base, 8 per link)
+With --locate, in ONE PROCESS PER SIZE, the reads located on the unitigs of their own table (kh_unitigs_locate*):
+  unitigs_begin          kh_unitigs_begin(1), as above
+  locate_first           a begin (not timed), then the first kh_unitigs_locate_device of 1 M reads: it builds the place map
+  index_build            locate_first minus locate_device; index_share = that over unitigs_begin
+  locate_device          kh_unitigs_locate_device of 1 M resident reads (151 M window starts) -- also as window starts / s and
+                         bytes / s of output; profile_device = kh_profile_device on the same reads, the two alternating
+  locate_pinned          kh_unitigs_locate from and into pinned memory; profile_pinned = kh_profile likewise, alternating
 The measurement runs in a child process with a timeout; a failure is reported as {"error": ...}."""
 import argparse
 import json
@@ -244,7 +251,72 @@ def measure_text_one(n, k):
     return out
 
 
+def measure_locate_one(n, k):
+    import numpy as np
+    import torch
+    from krust_amd import native
+    rl = 150
+    t = torch.empty(n * (rl + 1), dtype=torch.uint8, device="cuda:0")
+    native.synth_reads_device(t.data_ptr(), None, 20260130, 1 << 28, rl, 0, n, device=0)
+    torch.cuda.synchronize()
+    a = native.DeviceCounter(k, device=0)
+    a.push_device(t.data_ptr(), None, t.numel())
+    st = a.finish()
+    out = {"k": k, "reads": n, "table": {f: st[f] for f in ("distinct", "kmers", "table_slots", "slot_bytes")}}
+    begin = timed(lambda: a.unitigs_begin(1))
+    nu, nb = a.unitigs_begin(1)
+    out.update(nodes=st["distinct"], unitigs=nu, bases=nb, unitigs_begin=begin, index_bytes=8 * st["table_slots"])
+    m = min(n, 1_000_000) * (rl + 1)            # the reads that are located: the first million of the table's own
+    d_in = t[:m]
+    d_loc = torch.empty(m, dtype=torch.int64, device="cuda:0")
+    d_pro = torch.empty(m, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    out["window_starts"] = m
+
+    def alternating(f, g, reps=5):
+        """Medians of f and g, called in turn after one warm call of each."""
+        f(), g()
+        tf, tg = [], []
+        for _ in range(reps):
+            for fn, ts in ((f, tf), (g, tg)):
+                t0 = time.perf_counter()
+                fn()
+                ts.append(time.perf_counter() - t0)
+        tf.sort(), tg.sort()
+        return ({"median_s": tf[reps // 2], "spread_s": tf[-1] - tf[0]}, {"median_s": tg[reps // 2], "spread_s": tg[-1] - tg[0]})
+
+    firsts = []
+    for _ in range(5):                          # a begin releases the map: the next call builds it again
+        a.unitigs_begin(1)
+        t0 = time.perf_counter()
+        a.unitigs_locate_device(d_in, None, m, d_loc)
+        firsts.append(time.perf_counter() - t0)
+    firsts.sort()
+    out["locate_first"] = {"median_s": firsts[2], "spread_s": firsts[-1] - firsts[0]}
+    loc, pro = alternating(lambda: a.unitigs_locate_device(d_in, None, m, d_loc), lambda: a.profile_device(d_in, None, m, d_pro))
+    out["locate_device"] = dict(loc, starts_per_s=m / loc["median_s"], out_bytes_per_s=8 * m / loc["median_s"])
+    out["profile_device"] = dict(pro, starts_per_s=m / pro["median_s"], out_bytes_per_s=4 * m / pro["median_s"])
+    build = max(out["locate_first"]["median_s"] - loc["median_s"], 0.0)
+    out["index_build"] = {"median_s": build, "index_share": build / begin["median_s"]}
+    words, counts = d_loc.cpu().numpy().view(np.uint64), d_pro.cpu().numpy().view(np.uint32)
+    assert np.array_equal(words == np.uint64(native.LOC_NO_WINDOW), counts == native.PROFILE_NO_WINDOW)
+    assert np.array_equal(native.loc_is_place(words), (counts != native.PROFILE_NO_WINDOW) & (counts >= 1))
+    out["places"] = int(np.sum(native.loc_is_place(words)))
+    with native.PinnedArray(m) as pb, native.PinnedArray(m, np.uint64) as pl, native.PinnedArray(m, np.uint32) as pp:
+        pb.array[:] = d_in.cpu().numpy()
+        loc, pro = alternating(lambda: a.unitigs_locate(pb.array, out=pl.array), lambda: a.profile(pb.array, out=pp.array))
+        assert np.array_equal(pl.array, words) and np.array_equal(pp.array, counts)
+    out["locate_pinned"] = dict(loc, starts_per_s=m / loc["median_s"], out_bytes_per_s=8 * m / loc["median_s"])
+    out["profile_pinned"] = dict(pro, starts_per_s=m / pro["median_s"], out_bytes_per_s=4 * m / pro["median_s"])
+    a.unitigs_end()
+    a.close()
+    return out
+
+
 def measure(args):
+    if args.locate:
+        print("RESULT " + json.dumps([measure_locate_one(n, args.k) for n in args.reads]))
+        return
     if args.text:
         print("RESULT " + json.dumps([measure_text_one(n, args.k) for n in args.reads]))
         return
@@ -260,15 +332,17 @@ def main():
     ap.add_argument("--clip", action="store_true", help="kh_clip_tips_into beside kh_unitigs_begin_linked, nothing else")
     ap.add_argument("--pop", action="store_true", help="kh_pop_bubbles_into beside kh_clip_tips_into and kh_unitigs_begin_linked, nothing else")
     ap.add_argument("--text", action="store_true", help="kh_unitigs_text_* beside kh_unitigs_begin_linked and the copies, one process per size")
+    ap.add_argument("--locate", action="store_true", help="kh_unitigs_locate* beside kh_profile* and kh_unitigs_begin, one process per size")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
         measure(args)
         return
-    if args.text:   # one process per size
+    if args.text or args.locate:   # one process per size
+        which = "--locate" if args.locate else "--text"
         res = []
         for n in args.reads:
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--text", "--k", str(args.k), "--reads", str(n)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", which, "--k", str(args.k), "--reads", str(n)]
             try:
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
                 line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
@@ -279,7 +353,7 @@ def main():
             except subprocess.TimeoutExpired:
                 res.append({"reads": n, "error": f"no result within {args.timeout} s"})
                 break
-        print(json.dumps({"probe": "unitig-text", "result": res}, indent=1))
+        print(json.dumps({"probe": "unitig-locate" if args.locate else "unitig-text", "result": res}, indent=1))
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k)] + (["--clip"] if args.clip else []) + (["--pop"] if args.pop else []) + ["--reads"] + [str(n) for n in args.reads]
     try:
