@@ -134,6 +134,12 @@ pub mod sys {
         /// `out[i]` = where on the live unitigs the k-mer at window start i lies: 2 * unitig + sign above the offset, or a special
         pub fn kh_unitigs_locate_device(ctx: *mut KhCtx, d_bases: *const u8, d_qual: *const u8, n: u64, d_out: *mut u64) -> c_int;
         pub fn kh_unitigs_locate(ctx: *mut KhCtx, bases: *const u8, qual: *const u8, n: u64, out: *mut u64) -> c_int;
+        /// the same walk folded on the device into runs: `run_start` takes nrec + 1 CSR offsets, `runs` up to `run_cap` rows of 4 u32
+        /// (KH_RUN_* of the header), `cover` (may be null) 2 u64 per unitig that are added to; `KH_ERR_RANGE` when `run_cap` is too small
+        pub fn kh_unitigs_paths_device(ctx: *mut KhCtx, d_bases: *const u8, d_qual: *const u8, n: u64, d_rec_start: *const u64, nrec: u64,
+                                       d_run_start: *mut u64, d_runs: *mut u32, run_cap: u64, d_cover: *mut u64, n_runs: *mut u64) -> c_int;
+        pub fn kh_unitigs_paths(ctx: *mut KhCtx, bases: *const u8, qual: *const u8, n: u64, rec_start: *const u64, nrec: u64,
+                                run_start: *mut u64, runs: *mut u32, run_cap: u64, cover: *mut u64, n_runs: *mut u64) -> c_int;
         /// one round of tip clipping of `src`'s compacted graph at `min_count`: the k-mers of the surviving unitigs are added to `dst`
         /// (`count[key] += c`); `out` takes the 8 words KH_CLIP_* of the header names
         pub fn kh_clip_tips_into(dst: *mut KhCtx, src: *mut KhCtx, min_count: u64, max_kmers: u64, out: *mut u64) -> c_int;
@@ -249,6 +255,17 @@ pub const fn loc_unitig(w: u64) -> u32 { (w >> 33) as u32 }
 pub const fn loc_sign(w: u64) -> u32 { ((w >> 32) & 1) as u32 }
 /// `KH_LOC_OFFSET(w)`: the k-mer is bases offset .. offset + k of the unitig's reported sequence.
 pub const fn loc_offset(w: u64) -> u32 { (w & 0xFFFF_FFFF) as u32 }
+/// `KH_RUN_WORDS`: the u32 words of a run row of [`HipKmerMap::unitigs_paths`] -- `RUN_STATE` (2 * unitig + sign), `RUN_OFFSET` (of
+/// the run's first window in the unitig's reported sequence), `RUN_QSTART` and `RUN_QEND` (window starts relative to the record).
+pub const RUN_WORDS: usize = 4;
+pub const RUN_STATE: usize = 0;
+pub const RUN_OFFSET: usize = 1;
+pub const RUN_QSTART: usize = 2;
+pub const RUN_QEND: usize = 3;
+/// `KH_COV_WORDS`: the u64 words per unitig of the coverage array -- `COV_WINDOWS` (windows located on it), `COV_RUNS` (runs on it).
+pub const COV_WORDS: usize = 2;
+pub const COV_WINDOWS: usize = 0;
+pub const COV_RUNS: usize = 1;
 /// `KH_UNI_LINK_FROM(w)`: the unitig a link word of `kh_unitigs_links_copy` leaves (a row index of `kh_unitigs_copy`).
 pub const fn uni_link_from(w: u64) -> u32 { (w >> 33) as u32 }
 /// `KH_UNI_LINK_FROM_SIGN(w)`: 0 = it leaves the right end of the reported sequence (+), 1 = that of its reverse complement (-).
@@ -685,6 +702,45 @@ impl HipKmerMap {
         err?;
         check(self.ctx, end)?;
         Ok(out)
+    }
+
+    /// The records of `bases` as run-compressed walks over the unitigs of the table at `min_count` (`kh_unitigs_begin_linked` /
+    /// `kh_unitigs_paths` twice -- once to size, once to fill -- / `kh_unitigs_end`).  `rec_start` holds nrec + 1 ascending offsets into
+    /// the flat buffer.  Returns `(run_start, runs, cover)`: nrec + 1 CSR offsets, `RUN_WORDS` u32 per run (`RUN_STATE` ..
+    /// `RUN_QEND`; the runs of record r are rows `run_start[r] .. run_start[r + 1]`), and `COV_WORDS` u64 per unitig (windows, runs).
+    pub fn unitigs_paths(&self, min_count: u64, bases: &[u8], qual: Option<&[u8]>, rec_start: &[u64])
+                         -> Result<(Vec<u64>, Vec<u32>, Vec<u64>), HipError> {
+        if let Some(q) = qual {
+            if q.len() != bases.len() {
+                return Err(HipError::Device("qual must have the same length as bases".into()));
+            }
+        }
+        if rec_start.is_empty() {
+            return Err(HipError::Device("rec_start needs nrec + 1 offsets".into()));
+        }
+        let nrec = (rec_start.len() - 1) as u64;
+        let (mut nu, mut nb, mut nl) = (0u64, 0u64, 0u64);
+        check(self.ctx, unsafe { sys::kh_unitigs_begin_linked(self.ctx, min_count, &mut nu, &mut nb, &mut nl) })?;
+        let qp = qual.map_or(std::ptr::null(), |q| q.as_ptr());
+        let mut run_start = vec![0u64; rec_start.len()];
+        let mut cover = vec![0u64; nu as usize * COV_WORDS];
+        let mut total = 0u64;
+        let mut rc = unsafe {
+            sys::kh_unitigs_paths(self.ctx, bases.as_ptr(), qp, bases.len() as u64, rec_start.as_ptr(), nrec, run_start.as_mut_ptr(),
+                                  std::ptr::null_mut(), 0, std::ptr::null_mut(), &mut total)
+        };
+        let mut runs = vec![0u32; total as usize * RUN_WORDS];
+        if rc == -8 {  // KH_ERR_RANGE: there are runs -- now with room for them
+            rc = unsafe {
+                sys::kh_unitigs_paths(self.ctx, bases.as_ptr(), qp, bases.len() as u64, rec_start.as_ptr(), nrec, run_start.as_mut_ptr(),
+                                      runs.as_mut_ptr(), total, cover.as_mut_ptr(), &mut total)
+            };
+        }
+        let err = check(self.ctx, rc);  // (before kh_unitigs_end replaces the error text)
+        let end = unsafe { sys::kh_unitigs_end(self.ctx) };
+        err?;
+        check(self.ctx, end)?;
+        Ok((run_start, runs, cover))
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

@@ -69,7 +69,7 @@ typedef enum kh_status {
 /* Allocation failures: what KH_ERR_OOM leaves behind.  One rule per kind of call; the comments further down only add to it.
  *   - A READING call takes the table as it is and allocates only for itself: kh_result_size / _copy / _copy_device / _sorted*,
  *     kh_result_text_*, kh_histogram, kh_lookup, kh_profile*, kh_profile_records*, kh_compare, kh_graph_*, kh_unitigs_*,
- *     kh_unitigs_text_begin / kh_unitigs_text_next / kh_unitigs_text_next_device and the src side of kh_clip_tips_into / kh_pop_bubbles_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
+ *     kh_unitigs_text_begin / kh_unitigs_text_next / kh_unitigs_text_next_device, kh_unitigs_paths / kh_unitigs_paths_device and the src side of kh_clip_tips_into / kh_pop_bubbles_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
  *     allocation, the table is unchanged and the context is NOT poisoned: the same call can be made again.  What the call
  *     allocated is released, except the scratch the context keeps for the next such call where that had been allocated
  *     before the failure: the pinned staging chunks and the copy stream of the host forms, the scan scratch (not after the
@@ -573,6 +573,53 @@ int kh_unitigs_text_next_device(kh_ctx *ctx, uint8_t *d_buf, uint64_t cap, uint6
 #define KH_LOC_OFFSET(w) ((uint32_t)((uint64_t)(w) & 0xFFFFFFFFu))
 int kh_unitigs_locate_device(kh_ctx *ctx, const uint8_t *d_bases, const uint8_t *d_qual, uint64_t n, uint64_t *d_out);
 int kh_unitigs_locate(kh_ctx *ctx, const uint8_t *bases, const uint8_t *qual, uint64_t n, uint64_t *out);
+
+/* ---- the same walk as RUN-COMPRESSED PATHS: one row per stretch of a record along one unitig (read threading, GAF / P lines) - */
+/* Let W[0 .. n) be what kh_unitigs_locate* writes for the same bases, qual, n and context.  These calls fold W on the device
+ * into runs -- "unitig 17 + from offset 3 for 58 k-mers, then unitig 40 - ..." -- so that 16 bytes per run leave it, not 8 per base.
+ * RECORDS: rec_start has nrec + 1 ascending entries, rec_start[nrec] <= n (the rule of kh_profile_records).  Record r owns the
+ *   window starts rec_start[r] <= i < rec_start[r+1]; the segments need not coincide with separators; window starts outside
+ *   every record belong to no run.
+ * CONTINUATION: W[i+1] continues W[i] iff both are places, both have the same high word, and W[i+1]'s offset is W[i]'s offset + 1
+ *   (sign +) or - 1 (sign -).  A link crossing is no continuation and begins a new run: the closing link of a circular unitig
+ *   (offset L - 1 -> 0) and each turn of a homopolymer loop included.
+ * RUN: a maximal stretch of window starts of ONE record in which every window continues its predecessor.  A record boundary ends a
+ *   run even where W continues across it.  KH_LOC_ABSENT and KH_LOC_NO_WINDOW belong to no run: the gap between one run's QEND
+ *   and the next one's QSTART says how many there were.
+ * OUTPUT: run_start always gets all nrec + 1 entries, as CSR: the runs of record r are rows run_start[r] .. run_start[r+1], in
+ *   ascending QSTART, and run_start[nrec] = *n_runs, always the number of runs of the call (runs <= window starts).  An empty
+ *   record, or one without a place, has an empty range.  A row is KH_RUN_WORDS uint32 words (below).
+ *   run_cap < *n_runs: KH_ERR_RANGE; run_start and *n_runs are complete, the first run_cap rows hold unspecified values, nothing at
+ *   or behind row run_cap is written, cover is unchanged, the context is usable.  run_cap == 0 takes runs == NULL: how a caller sizes.
+ * COVERAGE: cover may be NULL; else n_unitigs * KH_COV_WORDS uint64 words, indexed by the row index of kh_unitigs_copy.  On KH_OK
+ *   only, cover[u][KH_COV_WINDOWS] += the windows of every run on u and cover[u][KH_COV_RUNS] += their number: a caller streams
+ *   batches into one array.  Device memory in the device form, host memory in the host form.
+ * OTHERWISE the contract of kh_unitigs_locate*: both enter as readers, need live unitigs of either begin (KH_ERR_STATE), leave
+ *   kh_stats and a kh_result_text_* or kh_unitigs_text_* stream alone, build the place map if no locate call has yet (the one
+ *   index: a later locate call finds it built, and the other way round), and follow the reading calls' KH_ERR_OOM rule: not
+ *   poisoned, unitigs live, nothing of the call stays allocated beyond what that rule lets a context keep.  The device form cuts its
+ *   input into the chunks of the host form.  nrec == 0: KH_OK, *n_runs = 0, nothing else written.  n == 0 with nrec > 0: all
+ *   run_start entries are 0.  An empty S gives 0 runs.
+ * KH_ERR_BAD_ARG (the context stays usable): NULL n_runs; NULL bases with n > 0; NULL rec_start or run_start with nrec > 0; NULL
+ *   runs with run_cap > 0; runs not 4-byte aligned; rec_start, run_start or cover not 8-byte aligned.  In the host form only:
+ *   rec_start not ascending, rec_start[nrec] > n, or a record of 2^32 or more window starts -- for the device form these three are
+ *   the caller's contract: offsets that break it give unspecified rows and never an access outside the arrays.
+ * WHAT FOLLOWS: expanding every run gives exactly the place words of W inside the records.  For a record R of m valid bases,
+ *   paths(rc(R)) is paths(R) reversed, with the sign flipped, OFFSET replaced by the run's last offset, and QSTART / QEND mirrored
+ *   in the m - k + 1 windows.  With kh_unitigs_begin_linked, consecutive runs of a record with QEND == the next QSTART are joined
+ *   by a link word. */
+#define KH_RUN_WORDS 4      /* uint32 words per run row */
+#define KH_RUN_STATE 0      /* 2 * unitig + sign: the high word of the run's first place, a link word's half */
+#define KH_RUN_OFFSET 1     /* offset of the run's FIRST window in the unitig's reported sequence (a '-' run descends from it) */
+#define KH_RUN_QSTART 2     /* first window start of the run, relative to its record's rec_start[r] */
+#define KH_RUN_QEND 3       /* one behind its last window start, relative to the same: the run has QEND - QSTART windows */
+#define KH_COV_WORDS 2      /* uint64 words per unitig of the coverage array */
+#define KH_COV_WINDOWS 0    /* window starts of the call's records located on the unitig, either sign */
+#define KH_COV_RUNS 1       /* runs on it */
+int kh_unitigs_paths_device(kh_ctx *ctx, const uint8_t *d_bases, const uint8_t *d_qual, uint64_t n, const uint64_t *d_rec_start,
+                            uint64_t nrec, uint64_t *d_run_start, uint32_t *d_runs, uint64_t run_cap, uint64_t *d_cover, uint64_t *n_runs);
+int kh_unitigs_paths(kh_ctx *ctx, const uint8_t *bases, const uint8_t *qual, uint64_t n, const uint64_t *rec_start,
+                     uint64_t nrec, uint64_t *run_start, uint32_t *runs, uint64_t run_cap, uint64_t *cover, uint64_t *n_runs);
 
 /* ---- tip clipping: one round of removing short dead-end branches (what assemblers do first with the compacted graph) --- */
 /* Take the unitigs and links of kh_unitigs_begin_linked(src, min_count): rows, end states (i, +) and (i, -) and link words exactly

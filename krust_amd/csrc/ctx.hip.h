@@ -11,6 +11,8 @@
 //   graph.hip     kh_graph_stats / kh_graph_masks*: the table against itself, eight probes per k-mer, its de Bruijn degrees out
 //   unitig.hip    kh_unitigs_*: the maximal non-branching paths of that graph (link rule, chain ranking by pointer doubling, emitter, links between them)
 //   unitig_text.hip  kh_unitigs_text_*: those unitigs and links as FASTA / GFA text, formatted on the device and streamed out in pieces
+//   locate.hip    kh_unitigs_locate*: where on those unitigs the k-mer of every window start of new sequences lies (the place map)
+//   paths.hip     kh_unitigs_paths*: those places folded per record into runs along one unitig, and the coverage per unitig
 //   sort.hip      kh_result_sorted*: the result pairs in ascending key order (a device radix sort; format.hip streams it as text)
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
@@ -607,6 +609,12 @@ u64 profile_chunk(const kh_ctx *c, u64 n);
 int profile_buffers(kh_ctx *c, u64 chunk, u64 out_bytes = 4, const char *who = "kh_profile: chunk buffers");
 // ---- locate.hip
 // (the place map is released by unitigs_release(): it is memory of the unitigs)
+// The place map of the live unitigs (Unitigs::where), built if no call has built it since their begin; on any failure nothing of it
+// stays and the status is a reading call's.  who: the call, for the error text.
+int locate_index(kh_ctx *c, const char *who);
+// The word of every window start i < nout of the n device-resident bytes -> d_out[i] (8-byte aligned); needs the place map;
+// asynchronous on the compute stream.  paths.hip runs it per chunk.
+int locate_range(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 n, u64 nout, u64 *d_out);
 
 // ---- stage timing: HIP events on the launch stream, resolved lazily ---------------------------
 struct StageTimer {

@@ -192,7 +192,6 @@ __global__ __launch_bounds__(BLOCK) void locate_kernel(const uint8_t *__restrict
 }  // namespace kh
 
 namespace khi {
-namespace {
 
 // The place map of the live unitigs, built if this is the first locate call since their begin.  On any failure nothing of it stays.
 int locate_index(kh_ctx *c, const char *who) {
@@ -273,6 +272,8 @@ int locate_range(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 n
     HIP_TRY(c, hipGetLastError());
     return KH_OK;
 }
+
+namespace {
 
 // What both calls do before they touch anything: arguments, entry, live unitigs.
 int locate_enter(kh_ctx *c, const char *who, const void *bases, uint64_t n, const void *out) {

@@ -108,6 +108,11 @@ def loc_is_place(words):
     return np.asarray(words, dtype=np.uint64) < np.uint64(LOC_ABSENT)
 
 
+# KH_RUN_*: the words of a run row of kh_unitigs_paths* -- state (2 * unitig + sign), offset of the run's first window in the unitig,
+# first window start and one behind the last, both relative to the record; KH_COV_*: the words per unitig of its coverage array
+RUN_WORDS, RUN_STATE, RUN_OFFSET, RUN_QSTART, RUN_QEND = 4, 0, 1, 2, 3
+COV_WORDS, COV_WINDOWS, COV_RUNS = 2, 0, 1
+
 # KH_CLIP_*: the words of kh_clip_tips_into
 CLIP_WORDS = 8
 CLIP_UNITIGS, CLIP_CANDIDATES, CLIP_CLIPPED, CLIP_CLIPPED_KMERS, CLIP_CLIPPED_COUNT, CLIP_KEPT_KMERS, CLIP_KEPT_COUNT, CLIP_LINKS = range(8)
@@ -199,6 +204,8 @@ SYMBOLS = {
     "kh_unitigs_text_next_device": (C.c_int, [_P, _P, _U64, C.POINTER(_U64)]),
     "kh_unitigs_locate_device": (C.c_int, [_P, _P, _P, _U64, _P]),
     "kh_unitigs_locate": (C.c_int, [_P, _P, _P, _U64, _P]),
+    "kh_unitigs_paths_device": (C.c_int, [_P, _P, _P, _U64, _P, _U64, _P, _P, _U64, _P, C.POINTER(_U64)]),
+    "kh_unitigs_paths": (C.c_int, [_P, _P, _P, _U64, _P, _U64, _P, _P, _U64, _P, C.POINTER(_U64)]),
     "kh_clip_tips_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_pop_bubbles_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
@@ -735,6 +742,55 @@ class DeviceCounter:
         words to fill (8-byte aligned), or torch tensors on this context's device.  Returns when d_out is complete."""
         ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
         self._check(lib().kh_unitigs_locate_device(self._h, ptr(d_bases), ptr(d_qual), int(n), ptr(d_out)))
+
+    # -- the same walk as run-compressed paths ---------------------------------
+    def unitigs_paths(self, bases, rec_start, qual=None, cover=None, run_cap=None):
+        """kh_unitigs_paths: the words of unitigs_locate(bases, qual) folded on the device into runs.  rec_start holds nrec + 1
+        ascending offsets into the flat buffer (record r owns the window starts rec_start[r] .. rec_start[r+1]; the last offset
+        <= len(bases)).  Returns (run_start, runs): nrec + 1 uint64 CSR offsets and an (n_runs, 4) uint32 array, columns RUN_STATE
+        (2 * unitig + sign), RUN_OFFSET (of the run's first window in the unitig), RUN_QSTART and RUN_QEND (window starts relative
+        to the record) -- the runs of record r are rows run_start[r] .. run_start[r+1].  cover: a uint64 array of n_unitigs *
+        COV_WORDS words that the call adds the windows and the runs per unitig to.  run_cap=None sizes with a first call
+        (run_cap 0); with a run_cap that is too small the call raises KmerHipError(KH_ERR_RANGE) and adds nothing to cover."""
+        bp, kb = _addr(bases)
+        n = kb.size if kb is not None else 0
+        qp, kq = _addr(qual)
+        if kq is not None and kq.size != n:
+            raise ValueError("qual must have the same length as bases")
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        if rs.ndim != 1 or rs.size < 1:
+            raise ValueError("rec_start needs nrec + 1 offsets")
+        nrec = rs.size - 1
+        if cover is not None:
+            assert cover.dtype == np.uint64 and cover.flags.c_contiguous and cover.flags.writeable
+        cp = None if cover is None else cover.ctypes.data
+        run_start = np.zeros(nrec + 1, dtype=np.uint64)
+        total = _U64(0)
+        if run_cap is None:
+            rc = lib().kh_unitigs_paths(self._h, bp, qp, n, rs.ctypes.data, nrec, run_start.ctypes.data, None, 0, None, C.byref(total))
+            if rc != KH_ERR_RANGE:
+                self._check(rc)
+                if cover is None:
+                    return run_start, np.empty((0, RUN_WORDS), dtype=np.uint32)
+            run_cap = total.value
+        runs = np.empty((int(run_cap), RUN_WORDS), dtype=np.uint32)
+        self._check(lib().kh_unitigs_paths(self._h, bp, qp, n, rs.ctypes.data, nrec, run_start.ctypes.data,
+                                           runs.ctypes.data if run_cap else None, int(run_cap), cp, C.byref(total)))
+        return run_start, runs[:total.value]
+
+    def unitigs_paths_device(self, d_bases, d_qual, n, d_rec_start, nrec, d_run_start, d_runs, run_cap, d_cover=None):
+        """The same on device memory: integer addresses or torch tensors of n bases, n quality bytes or None, nrec + 1 uint64
+        offsets (the caller's contract, not checked), nrec + 1 uint64 words and run_cap * 4 uint32 words to fill, and n_unitigs * 2
+        uint64 words to add to, or None.  Returns (status, n_runs) with status KH_OK or KH_ERR_RANGE -- run_cap was too small:
+        n_runs and d_run_start are complete, size d_runs and call again --, and raises for every other status.  Returns when the
+        outputs are complete."""
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        total = _U64(0)
+        rc = lib().kh_unitigs_paths_device(self._h, ptr(d_bases), ptr(d_qual), int(n), ptr(d_rec_start), int(nrec), ptr(d_run_start),
+                                           ptr(d_runs), int(run_cap), ptr(d_cover), C.byref(total))
+        if rc != KH_ERR_RANGE:
+            self._check(rc)
+        return rc, total.value
 
     # -- tip clipping: one round over the compacted graph ---------------------
     def clip_tips_into(self, src, min_count=1, max_kmers=None):

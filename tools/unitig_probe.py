@@ -37,6 +37,13 @@ With --locate, in ONE PROCESS PER SIZE, the reads located on the unitigs of thei
   locate_device          kh_unitigs_locate_device of 1 M resident reads (151 M window starts) -- also as window starts / s and
                          bytes / s of output; profile_device = kh_profile_device on the same reads, the two alternating
   locate_pinned          kh_unitigs_locate from and into pinned memory; profile_pinned = kh_profile likewise, alternating
+With --paths, in ONE PROCESS PER SIZE, the same resident reads as run-compressed paths (kh_unitigs_paths*), one record per read:
+  runs, runs_per_read    the runs of the 1 M reads; bytes_out = 16 per run + 8 per read, against locate's 8 per window start
+  paths_device           kh_unitigs_paths_device with room for every run and a coverage array; locate_device = kh_unitigs_locate_device
+                         on the same reads, the two alternating; paths_over_locate = the ratio of the medians
+  paths_pinned           kh_unitigs_paths from pinned memory into pinned arrays; locate_pinned = kh_unitigs_locate likewise, alternating
+  split_ms               the device form's time on the device per step -- locate_range, path_flags_kernel, the scan, path_emit_kernel,
+                         path_cover_kernel -- from HIP events round every launch (a second context with KH_FLAG_TRACE, one call)
 The measurement runs in a child process with a timeout; a failure is reported as {"error": ...}."""
 import argparse
 import json
@@ -313,7 +320,101 @@ def measure_locate_one(n, k):
     return out
 
 
+def measure_paths_one(n, k):
+    import ctypes as C
+    import re
+    import tempfile
+    import numpy as np
+    import torch
+    from krust_amd import native
+    rl = 150
+    t = torch.empty(n * (rl + 1), dtype=torch.uint8, device="cuda:0")
+    native.synth_reads_device(t.data_ptr(), None, 20260130, 1 << 28, rl, 0, n, device=0)
+    torch.cuda.synchronize()
+    nrec = min(n, 1_000_000)
+    m = nrec * (rl + 1)                         # the reads that are walked: the first million of the table's own
+    d_in = t[:m]
+    rs = np.arange(0, m + 1, rl + 1, dtype=np.uint64)
+    d_rs = torch.from_numpy(rs.view(np.int64)).cuda()
+    d_st = torch.empty(nrec + 1, dtype=torch.int64, device="cuda:0")
+    d_loc = torch.empty(m, dtype=torch.int64, device="cuda:0")
+    out = {"k": k, "reads": n, "records": nrec, "window_starts": m}
+
+    def alternating(f, g, reps=5):
+        f(), g()
+        tf, tg = [], []
+        for _ in range(reps):
+            for fn, ts in ((f, tf), (g, tg)):
+                t0 = time.perf_counter()
+                fn()
+                ts.append(time.perf_counter() - t0)
+        tf.sort(), tg.sort()
+        return ({"median_s": tf[reps // 2], "spread_s": tf[-1] - tf[0]}, {"median_s": tg[reps // 2], "spread_s": tg[-1] - tg[0]})
+
+    def table(trace):
+        a = native.DeviceCounter(k, device=0, trace=trace)
+        a.push_device(t.data_ptr(), None, t.numel())
+        a.finish()
+        return a, a.unitigs_begin(1)
+
+    a, (nu, nb) = table(False)
+    d_cov = torch.zeros(nu * native.COV_WORDS, dtype=torch.int64, device="cuda:0")
+    rc, runs = a.unitigs_paths_device(d_in, None, m, d_rs, nrec, d_st, None, 0, None)      # sizes, and builds the place map
+    d_runs = torch.empty(max(runs, 1) * native.RUN_WORDS, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    out.update(unitigs=nu, runs=runs, runs_per_read=runs / nrec, bytes_out=16 * runs + 8 * (nrec + 1), locate_bytes_out=8 * m)
+    pth, loc = alternating(lambda: a.unitigs_paths_device(d_in, None, m, d_rs, nrec, d_st, d_runs, runs, d_cov),
+                           lambda: a.unitigs_locate_device(d_in, None, m, d_loc))
+    out["paths_device"] = dict(pth, starts_per_s=m / pth["median_s"])
+    out["locate_device"] = dict(loc, starts_per_s=m / loc["median_s"])
+    out["paths_over_locate_device"] = pth["median_s"] / loc["median_s"]
+    rows = d_runs.cpu().numpy().view(np.uint32).reshape(-1, native.RUN_WORDS)[:runs]
+    words = d_loc.cpu().numpy().view(np.uint64)
+    windows = int((rows[:, native.RUN_QEND] - rows[:, native.RUN_QSTART]).astype(np.int64).sum())
+    assert windows == int(np.sum(native.loc_is_place(words)))      # every place lies in one run (a read's separator is no window)
+    out["places"] = windows
+    with native.PinnedArray(m) as pb, native.PinnedArray(m, np.uint64) as pl, native.PinnedArray(nrec + 1, np.uint64) as ps, \
+            native.PinnedArray(max(runs, 1) * native.RUN_WORDS, np.uint32) as pr, native.PinnedArray(nu * native.COV_WORDS, np.uint64) as pc:
+        pb.array[:] = d_in.cpu().numpy()
+        pc.array[:] = 0
+        total = C.c_uint64(0)
+
+        def host_paths():
+            rc = native.lib().kh_unitigs_paths(a._h, pb.array.ctypes.data, None, m, rs.ctypes.data, nrec, ps.array.ctypes.data, pr.array.ctypes.data,
+                                               runs, pc.array.ctypes.data, C.byref(total))
+            assert rc == native.KH_OK and total.value == runs
+        pth, loc = alternating(host_paths, lambda: a.unitigs_locate(pb.array, out=pl.array))
+        assert np.array_equal(pr.array.reshape(-1, native.RUN_WORDS)[:runs], rows) and np.array_equal(pl.array, words)
+    out["paths_pinned"] = dict(pth, starts_per_s=m / pth["median_s"])
+    out["locate_pinned"] = dict(loc, starts_per_s=m / loc["median_s"])
+    out["paths_over_locate_pinned"] = pth["median_s"] / loc["median_s"]
+    a.unitigs_end()
+    a.close()
+    # the split: one traced call of a second context, its line read back from the process's stderr
+    b, _ = table(True)
+    b.unitigs_paths_device(d_in, None, m, d_rs, nrec, d_st, d_runs, runs, d_cov)           # (warm: builds the place map)
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            b.unitigs_paths_device(d_in, None, m, d_rs, nrec, d_st, d_runs, runs, d_cov)
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        text = tmp.read().decode(errors="replace")
+    line = [l for l in text.splitlines() if "kh_unitigs_paths_device:" in l]
+    out["split_ms"] = {name: float(v) for name, v in re.findall(r"(\w+) ([0-9.]+) ms", line[-1])} if line else {"error": text[-500:]}
+    b.unitigs_end()
+    b.close()
+    return out
+
+
 def measure(args):
+    if args.paths:
+        print("RESULT " + json.dumps([measure_paths_one(n, args.k) for n in args.reads]))
+        return
     if args.locate:
         print("RESULT " + json.dumps([measure_locate_one(n, args.k) for n in args.reads]))
         return
@@ -333,13 +434,14 @@ def main():
     ap.add_argument("--pop", action="store_true", help="kh_pop_bubbles_into beside kh_clip_tips_into and kh_unitigs_begin_linked, nothing else")
     ap.add_argument("--text", action="store_true", help="kh_unitigs_text_* beside kh_unitigs_begin_linked and the copies, one process per size")
     ap.add_argument("--locate", action="store_true", help="kh_unitigs_locate* beside kh_profile* and kh_unitigs_begin, one process per size")
+    ap.add_argument("--paths", action="store_true", help="kh_unitigs_paths* beside kh_unitigs_locate* on the reads of --locate, one process per size")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
         measure(args)
         return
-    if args.text or args.locate:   # one process per size
-        which = "--locate" if args.locate else "--text"
+    if args.text or args.locate or args.paths:   # one process per size
+        which = "--paths" if args.paths else "--locate" if args.locate else "--text"
         res = []
         for n in args.reads:
             cmd = [sys.executable, os.path.abspath(__file__), "--child", which, "--k", str(args.k), "--reads", str(n)]
@@ -353,7 +455,7 @@ def main():
             except subprocess.TimeoutExpired:
                 res.append({"reads": n, "error": f"no result within {args.timeout} s"})
                 break
-        print(json.dumps({"probe": "unitig-locate" if args.locate else "unitig-text", "result": res}, indent=1))
+        print(json.dumps({"probe": "unitig-paths" if args.paths else "unitig-locate" if args.locate else "unitig-text", "result": res}, indent=1))
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k)] + (["--clip"] if args.clip else []) + (["--pop"] if args.pop else []) + ["--reads"] + [str(n) for n in args.reads]
     try:
