@@ -6,7 +6,7 @@
 //   input.hip     kh_push* / kh_push_text*: staging, device accumulation, record scanning
 //   merge.hip     exports and merges of one context (pairs, dense, region-ordered)
 //   format.hip    kh_result_text_*: the table formatted as text on the device and streamed out in pieces
-//   profile.hip   kh_profile*: the table's count at every window start of new sequences
+//   profile.hip   kh_profile*: the table's count at every window start of new sequences; the chunk pipeline and launch plan of every read-side call
 //   join.hip      kh_compare / kh_combine_into: one table scanned, another probed, statistics or a third table out
 //   graph.hip     kh_graph_stats / kh_graph_masks*: the table against itself, eight probes per k-mer, its de Bruijn degrees out
 //   unitig.hip    kh_unitigs_*: the maximal non-branching paths of that graph (link rule, chain ranking by pointer doubling, emitter, links between them)
@@ -35,6 +35,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <new>
@@ -383,13 +384,13 @@ struct kh_ctx {
     u64 *ts_skey = nullptr;       u64 ts_skey_cap = 0;   // a sorted stream's pairs: the stream's own memory, never where its chunks live
     u64 *ts_scnt = nullptr;       u64 ts_scnt_cap = 0;
 
-    // ---- kh_profile: the chunks of the host form (profile.hip) ----
-    // two device buffers [bases | qualities | profile] for pf_chunk window starts each, their pinned twins (the bounce of pageable
-    // caller memory), and per buffer the events "input is on the device", "kernel done", "profile is in host memory"
+    // ---- the chunks of the four host forms of the read side (chunk_pipeline(), profile.hip) ----
+    // two device buffers [bases | qualities | results or words] for pf_chunk window starts each, their pinned twins (the bounce of
+    // pageable caller memory), and per buffer the events "input is on the device", "kernel done", "results are in host memory"
     uint8_t *pf_d[2] = {nullptr, nullptr};
     uint8_t *pf_h[2] = {nullptr, nullptr};
     u64 pf_chunk = 0;
-    u64 pf_out_bytes = 0;  // bytes per window start of the buffers' last part: 4 (kh_profile) or 8 (kh_unitigs_locate)
+    u64 pf_out_bytes = 0;  // bytes per window start of the buffers' last part: 4 (kh_profile, kh_profile_records) or 8 (kh_unitigs_locate, kh_unitigs_paths)
     hipEvent_t pf_in[2] = {nullptr, nullptr}, pf_run[2] = {nullptr, nullptr}, pf_out[2] = {nullptr, nullptr};
     // kh_profile_records: the rows (KH_REC_WORDS words per record) and the record offsets, on the device for the whole call
     uint32_t *pr_rows = nullptr;  u64 pr_rows_cap = 0;  // records
@@ -599,15 +600,55 @@ inline unsigned uni_grid(u64 items) { return (unsigned)grid_for(items); }  // ev
 // ---- unitig_text.hip
 void unitigs_text_release(kh_ctx *c);  // the offsets, chunks and events of a kh_unitigs_text_* stream (unitigs_release calls it)
 // ---- profile.hip
-void profile_release(kh_ctx *c);  // kh_destroy: the chunk buffers and events of kh_profile, the rows of kh_profile_records
-// The chunks of a host form that streams a flat buffer through the device (kh_profile, kh_profile_records, kh_unitigs_locate):
-// window starts per chunk, sized from the call (KMERHIP_PROFILE_CHUNK_KB in the test build), and the two device buffers
-// [bases | qualities | out_bytes per window start] with their pinned twins and events.  who: the call, for the error text.
+void profile_release(kh_ctx *c);  // kh_destroy: the chunk buffers and events of the host forms, the rows of kh_profile_records
+// The chunks of a host form that streams a flat buffer through the device (kh_profile, kh_profile_records, kh_unitigs_locate,
+// kh_unitigs_paths): window starts per chunk, sized from the call (KMERHIP_PROFILE_CHUNK_KB in the test build), and the two device
+// buffers [bases | qualities | out_bytes per window start] with their pinned twins and events.  who: the call, for the error text.
 constexpr u64 PF_PAD = 64;  // behind a chunk's bases: its k - 1 bytes of the next chunk, and the kernel's 16-byte loads
 inline u64 pf_in_stride(u64 chunk) { return (chunk + PF_PAD + 15) & ~15ull; }
 u64 profile_chunk(const kh_ctx *c, u64 n);
 int profile_buffers(kh_ctx *c, u64 chunk, u64 out_bytes = 4, const char *who = "kh_profile: chunk buffers");
+// One chunk of chunk_pipeline(), as its launch sees it: chunk j owns the ns window starts from a; len bytes lie at d_bases (and at
+// d_qual, nullptr without a quality filter) from window start a on -- from a - 1 with a halo, except in front of the call's first;
+// d_tail: the buffer's last part, behind the bases and qualities.
+struct ChunkJob {
+    u64 j, a, ns;
+    const uint8_t *d_bases, *d_qual;
+    u64 len;
+    uint8_t *d_tail;
+};
+// The pipeline of all four host forms: n bytes of a flat host buffer in chunks of `chunk` window starts through the two buffers of
+// profile_buffers() (which the caller has called), launch(job) per chunk on the compute stream.  Chunk j is sent the bytes its
+// window starts need: its own and the k - 1 after them, with halo = 1 also one window start in front and one behind.  out: out_bytes
+// per window start come back from d_tail, on a stream of their own beside the kernel of chunk j + 1; nullptr: nothing comes back,
+// and the loop keeps one kernel ahead of the host.  Pinned caller memory is copied from and to directly, pageable memory through
+// the pinned twins.  The first failing step returns, with whatever is queued left in flight.
+int chunk_pipeline(kh_ctx *c, const uint8_t *bases, const uint8_t *qual, u64 n, u64 chunk, u64 halo, void *out, u64 out_bytes,
+                   const std::function<int(const ChunkJob &)> &launch);
+// Whether a call filters by quality (qualities given and a threshold set), and the byte it compares with then: minq + 33,
+// saturating at 255 (saturating_add(33) on u8, run.rs:538).
+inline bool qual_filter(const kh_ctx *c, const void *qual, uint32_t *thr = nullptr) {
+    const bool on = qual != nullptr && c->minq >= 0;
+    if (thr) *thr = on ? (uint32_t)std::min(c->minq + 33, 255) : 0u;
+    return on;
+}
+// The launch of a read-side kernel (profile_kernel, profile_records_kernel, locate_kernel) over the window starts i < nout of n
+// device-resident bytes: the data in virtual positions [vbeg, vend) over the 16-byte-aligned abase (qbase: the same coordinates;
+// nullptr, 0, 0 without a quality filter), tiles of kh::TILE positions, tpb contiguous ones per workgroup (the look-back is carried
+// in LDS), at most grid_cap() workgroups.  The window that starts at entry i ends at position vbeg + i + k - 1.
+struct ReadPlan {
+    const uint8_t *abase, *qbase;
+    int qaligned;
+    u64 vbeg, vend, ntiles;
+    uint32_t tpb, thr;
+    unsigned blocks;
+};
+ReadPlan read_plan(const kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 n, u64 nout);
+// What the record forms hold rec_start to (host memory): ascending, no record of 2^32 or more window starts, the last end within n.
+int check_rec_start(kh_ctx *c, const char *who, const u64 *rec_start, u64 nrec, u64 n);
 // ---- locate.hip
+// The end of what kh_unitigs_locate* and kh_unitigs_paths* do before they touch anything: enter for reading, the unitigs live.
+int enter_unitigs(kh_ctx *c, const char *who);
 // (the place map is released by unitigs_release(): it is memory of the unitigs)
 // The place map of the live unitigs (Unitigs::where), built if no call has built it since their begin; on any failure nothing of it
 // stays and the status is a reading call's.  who: the call, for the error text.

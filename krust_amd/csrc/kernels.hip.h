@@ -373,6 +373,27 @@ __device__ __forceinline__ WinCtx stage_tile(uint32_t (*s_code)[NT + 2], uint16_
     return stage_tile_raw<QUAL, NT>(s_code, s_val, buf, first, tid, raw, abase, qbase, qaligned, t, vbeg, vend, thr);
 }
 
+// The first index i of [lo, hi) at which below(i) is false (hi: none), for a predicate that is true up to some index and false
+// from there on -- "a[i] < key" over an ascending array --, by a whole workgroup of BLOCK lanes: a 256-ary search, one probe per
+// lane and round (profile_records_kernel looks for its first record with it, path_flags_kernel for a tile's first boundary).
+// Every lane returns the same index; a predicate that is not monotone gives some index in [lo, hi].
+template <typename BELOW>
+__device__ __forceinline__ u64 wg_first_not(u64 lo, u64 hi, int tid, BELOW below) {
+    while (lo < hi) {
+        const u64 step = (hi - lo + BLOCK - 1) / BLOCK;
+        const u64 idx = lo + (u64)tid * step;
+        const int c = __syncthreads_count(idx < hi && below(idx));
+        if (c == 0) {
+            hi = lo;
+        } else {
+            const u64 nh = lo + (u64)c * step;
+            lo = lo + (u64)(c - 1) * step + 1;
+            if (nh < hi) hi = nh;
+        }
+    }
+    return lo;
+}
+
 // Rolling canonical-window state of one lane over its 16 bases.  All 32-bit arithmetic:
 //   f  = the last 32 bases as a 64-bit shift register (two words), newest base in the low bits
 //   rc = reverse complement of the last k bases in the low 2k bits

@@ -111,6 +111,8 @@ __device__ __forceinline__ int lc_lds(int e) { return e + (e >> 4); }
 // are in flight before the first is looked at, then all where loads before the first is used.  The results are 8 bytes: a tile's
 // 4096 go through 32 KiB of LDS and leave as 16-byte stores at 16-byte-aligned addresses, two words each, with single words only
 // in front of the first aligned unit, behind the last, and at the two ends of out.
+// The first half is not profile_kernel's text on purpose: the loads here are branch-free and the trip count is 32-bit, because this
+// kernel has no scalar registers to spare for the masks of guarded loads.
 // kernel-resource-usage (gfx950, hipcc -O3): see DESIGN.md 4.16.
 template <bool QUAL, typename TAB>
 __global__ __launch_bounds__(BLOCK) void locate_kernel(const uint8_t *__restrict__ abase, const uint8_t *__restrict__ qbase, int qaligned,
@@ -241,35 +243,31 @@ int locate_index(kh_ctx *c, const char *who) {
     return KH_OK;
 }
 
-// Every window start i < nout of the n device-resident bytes -> d_out[i]; asynchronous on the compute stream.  The grid is
-// profile_range's: grid_cap(), contiguous tiles per workgroup.
+// Every window start i < nout of the n device-resident bytes -> d_out[i]; asynchronous on the compute stream.  The launch is
+// profile_range's: read_plan().
 int locate_range(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 n, u64 nout, u64 *d_out) {
     if (nout == 0) return KH_OK;
-    const u64 lead = (uintptr_t)d_bases & 15;
-    const uint8_t *abase = d_bases - lead;
-    const u64 vbeg = lead, vend = lead + n;
-    const bool use_qual = d_qual != nullptr && c->minq >= 0;
-    const uint8_t *qbase = use_qual ? d_qual - lead : nullptr;  // same virtual coordinates as the bases
-    const int qaligned = use_qual && (((uintptr_t)qbase) & 15) == 0;
-    uint32_t thr = 0;
-    if (use_qual) {
-        const int t = c->minq + 33;
-        thr = (uint32_t)(t > 255 ? 255 : t);
-    }
-    const u64 ntiles = (vbeg + (c->k - 1) + nout + kh::TILE - 1) / kh::TILE;
-    u64 blocks = ntiles < (u64)grid_cap() ? ntiles : (u64)grid_cap();
-    const uint32_t tpb = (uint32_t)((ntiles + blocks - 1) / blocks);
-    blocks = (ntiles + tpb - 1) / tpb;
+    const ReadPlan p = read_plan(c, d_bases, d_qual, n, nout);
+    const dim3 grid(p.blocks), block(kh::BLOCK);
     with_probe(c, [&](auto tab) {
         typedef decltype(tab) TAB;
-        if (use_qual)
-            hipLaunchKernelGGL((kh::locate_kernel<true, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase, qbase, qaligned,
-                               (uint32_t)vbeg, vend, ntiles, tpb, c->k, thr, tab, (const u64 *)c->un.where, d_out, nout);
+        if (p.qbase)
+            hipLaunchKernelGGL((kh::locate_kernel<true, TAB>), grid, block, 0, c->stream, p.abase, p.qbase, p.qaligned, (uint32_t)p.vbeg, p.vend, p.ntiles,
+                               p.tpb, c->k, p.thr, tab, (const u64 *)c->un.where, d_out, nout);
         else
-            hipLaunchKernelGGL((kh::locate_kernel<false, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase,
-                               (const uint8_t *)nullptr, 0, (uint32_t)vbeg, vend, ntiles, tpb, c->k, 0u, tab, (const u64 *)c->un.where, d_out, nout);
+            hipLaunchKernelGGL((kh::locate_kernel<false, TAB>), grid, block, 0, c->stream, p.abase, p.qbase, p.qaligned, (uint32_t)p.vbeg, p.vend, p.ntiles,
+                               p.tpb, c->k, p.thr, tab, (const u64 *)c->un.where, d_out, nout);
     });
     HIP_TRY(c, hipGetLastError());
+    return KH_OK;
+}
+
+int enter_unitigs(kh_ctx *c, const char *who) {
+    const int rc = enter(c, ENTER_READ);
+    if (rc != KH_OK) return rc;
+    if (!c->un.live)
+        return fail(c, KH_ERR_STATE,
+                    (std::string(who) + ": no unitigs: kh_unitigs_begin first (anything that changes the table makes them stale)").c_str());
     return KH_OK;
 }
 
@@ -281,11 +279,7 @@ int locate_enter(kh_ctx *c, const char *who, const void *bases, uint64_t n, cons
     const std::string w(who);
     if (n && (!bases || !out)) return fail(c, KH_ERR_BAD_ARG, (w + ": NULL argument").c_str());
     if ((uintptr_t)out & 7) return fail(c, KH_ERR_BAD_ARG, (w + ": the output is not 8-byte aligned").c_str());
-    int rc = enter(c, ENTER_READ);
-    if (rc != KH_OK) return rc;
-    if (!c->un.live)
-        return fail(c, KH_ERR_STATE, (w + ": no unitigs: kh_unitigs_begin first (anything that changes the table makes them stale)").c_str());
-    return KH_OK;
+    return enter_unitigs(c, who);
 }
 
 }  // namespace
@@ -306,44 +300,12 @@ extern "C" int kh_unitigs_locate(kh_ctx *c, const uint8_t *bases, const uint8_t 
     int rc = locate_enter(c, "kh_unitigs_locate", bases, n, out);
     if (rc != KH_OK) return rc;
     if (n == 0) return KH_OK;
-    const bool with_qual = qual != nullptr && c->minq >= 0;
     const u64 chunk = profile_chunk(c, n);
     // (the staging first: whichever allocation fails, nothing of the place map stays behind)
     if ((rc = profile_buffers(c, chunk, sizeof(u64), "kh_unitigs_locate: chunk buffers")) != KH_OK) return rc;
     if ((rc = locate_index(c, "kh_unitigs_locate")) != KH_OK) return rc;
-    // kh_profile's pipeline with 8 bytes per window start: chunk j owns the window starts [j chunk, (j + 1) chunk) and is sent the
-    // bytes they need, its own and the k - 1 after them; its places travel back on a stream of their own beside the kernel of chunk j + 1
-    const bool in_direct = is_pinned_host(bases) && (!with_qual || is_pinned_host(qual));
-    const bool out_direct = is_pinned_host(out);
-    const u64 stride = pf_in_stride(c->pf_chunk), k1 = c->k - 1;
-    const u64 nch = (n + chunk - 1) / chunk;
-    auto starts = [&](u64 j) { return std::min(chunk, n - j * chunk); };
-    auto finish = [&](u64 j) -> int {  // chunk j has arrived in pinned memory: out of the bounce buffer
-        const int b = (int)(j & 1);
-        HIP_TRY(c, hipEventSynchronize(c->pf_out[b]));
-        if (!out_direct) staged_memcpy(out + j * chunk, c->pf_h[b] + 2 * stride, sizeof(u64) * starts(j));
-        return KH_OK;
-    };
-    for (u64 j = 0; j < nch; ++j) {
-        // (the buffers of chunk j were those of chunk j - 2, which finish() saw complete in the last round)
-        const int b = (int)(j & 1);
-        const u64 a = j * chunk, ns = starts(j), len = std::min(ns + k1, n - a);
-        uint8_t *const d = c->pf_d[b], *const h = c->pf_h[b];
-        if (!in_direct) {
-            staged_memcpy(h, bases + a, len);
-            if (with_qual) staged_memcpy(h + stride, qual + a, len);
-        }
-        HIP_TRY(c, hipMemcpyAsync(d, in_direct ? bases + a : h, len, hipMemcpyHostToDevice, c->cstream));
-        if (with_qual) HIP_TRY(c, hipMemcpyAsync(d + stride, in_direct ? qual + a : h + stride, len, hipMemcpyHostToDevice, c->cstream));
-        HIP_TRY(c, hipEventRecord(c->pf_in[b], c->cstream));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pf_in[b], 0));
-        u64 *const d_out = reinterpret_cast<u64 *>(d + 2 * stride);
-        if ((rc = locate_range(c, d, with_qual ? d + stride : nullptr, len, ns, d_out)) != KH_OK) return rc;
-        HIP_TRY(c, hipEventRecord(c->pf_run[b], c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->cstream2, c->pf_run[b], 0));
-        HIP_TRY(c, hipMemcpyAsync(out_direct ? (void *)(out + a) : (void *)(h + 2 * stride), d_out, sizeof(u64) * ns, hipMemcpyDeviceToHost, c->cstream2));
-        HIP_TRY(c, hipEventRecord(c->pf_out[b], c->cstream2));
-        if (j && (rc = finish(j - 1)) != KH_OK) return rc;
-    }
-    return finish(nch - 1);
+    // kh_profile's pipeline with 8 bytes per window start
+    return chunk_pipeline(c, bases, qual, n, chunk, 0, out, sizeof(u64), [&](const ChunkJob &job) {
+        return locate_range(c, job.d_bases, job.d_qual, job.len, job.ns, reinterpret_cast<u64 *>(job.d_tail));
+    });
 }

@@ -21,26 +21,6 @@ constexpr int PT_LDS = TILE + 2 + (TILE + 2) / 16 + 1;
 __device__ __forceinline__ int pt_lds(int p) { return p + (p >> 4); }
 constexpr int PT_RB = TILE / 32 + 2;  // record starts at the tile's entries 0 .. 4096, one bit each
 
-// The first index i < cnt with a[i] >= key (cnt: none) of an ascending array, by the whole workgroup: 256 probes per round, as
-// profile_records_kernel looks for its first record.  Every lane returns the same index; an array that does not ascend gives some
-// index in [0, cnt].
-__device__ __forceinline__ u64 pt_first_at_least(const u64 *__restrict__ a, u64 cnt, u64 key, int tid) {
-    u64 lo = 0, hi = cnt;
-    while (lo < hi) {
-        const u64 step = (hi - lo + BLOCK - 1) / BLOCK;
-        const u64 idx = lo + (u64)tid * step;
-        const int c = __syncthreads_count(idx < hi && a[idx] < key);
-        if (c == 0) {
-            hi = lo;
-        } else {
-            const u64 nh = lo + (u64)c * step;
-            lo = lo + (u64)(c - 1) * step + 1;
-            if (nh < hi) hi = nh;
-        }
-    }
-    return lo;
-}
-
 // Heads and tails of one chunk.  wq[e] is the word of the chunk's entry e, window start G0 + e of the call, for -1 <= e <= ns (the
 // two outer ones KH_LOC_NO_WINDOW where the call has no such window start); wq is 16-byte aligned.  Per tile the words come to LDS
 // with 16-byte loads, the record boundaries that fall on the tile's entries 0 .. 4096 are marked in an LDS bitmap (a 256-ary
@@ -83,7 +63,7 @@ __global__ __launch_bounds__(BLOCK) void path_flags_kernel(const u64 *__restrict
         __syncthreads();
 
         const u64 Gs = G0 + tE;
-        u64 b0 = pt_first_at_least(rec_start, nrec + 1, Gs, tid);
+        u64 b0 = wg_first_not(0, nrec + 1, tid, [&](u64 i) { return rec_start[i] < Gs; });
         if (tid == 0) first[t] = b0;  // (path_emit_kernel goes on from there)
         for (;;) {  // (uniform: the count below is every lane's)
             const u64 idx = b0 + (u64)tid;
@@ -399,7 +379,8 @@ int path_cover(kh_ctx *c, const uint32_t *d_runs, u64 total, u64 *d_cover, PathT
 }
 
 // The host form's results out of device memory, once the compute stream has run dry: through the pinned twin of the first chunk
-// buffer, which nothing uses any more -- no allocation behind the place map's.  add: 64-bit words, added to what dst holds.
+// buffer, which nothing uses any more.  Not d2h_staged(): that may allocate its staging, and this call allocates nothing behind the
+// place map, so that no failure leaves one behind.  add: 64-bit words, added to what dst holds.
 int path_d2h(kh_ctx *c, void *dst, const void *d_src, u64 bytes, bool add) {
     const u64 room = (2 * pf_in_stride(c->pf_chunk) + c->pf_out_bytes * c->pf_chunk) & ~7ull;
     for (u64 off = 0; off < bytes; off += room) {
@@ -428,11 +409,7 @@ int paths_enter(kh_ctx *c, const char *who, const void *bases, u64 n, const void
     if (((uintptr_t)rec_start | (uintptr_t)run_start | (uintptr_t)cover) & 7)
         return fail(c, KH_ERR_BAD_ARG, (w + ": rec_start, run_start or cover is not 8-byte aligned").c_str());
     if (run_cap > (~0ull) / (KH_RUN_WORDS * sizeof(uint32_t))) return fail(c, KH_ERR_BAD_ARG, (w + ": run_cap is beyond any array").c_str());
-    int rc = enter(c, ENTER_READ);
-    if (rc != KH_OK) return rc;
-    if (!c->un.live)
-        return fail(c, KH_ERR_STATE, (w + ": no unitigs: kh_unitigs_begin first (anything that changes the table makes them stale)").c_str());
-    return KH_OK;
+    return enter_unitigs(c, who);
 }
 
 }  // namespace
@@ -484,18 +461,14 @@ extern "C" int kh_unitigs_paths(kh_ctx *c, const uint8_t *bases, const uint8_t *
     static const char who[] = "kh_unitigs_paths";
     int rc = paths_enter(c, who, bases, n, rec_start, nrec, run_start, runs, run_cap, cover, n_runs);
     if (rc != KH_OK) return rc;
-    for (u64 r = 0; r < nrec; ++r) {
-        if (rec_start[r] > rec_start[r + 1]) return fail(c, KH_ERR_BAD_ARG, "kh_unitigs_paths: rec_start is not ascending");
-        if (rec_start[r + 1] - rec_start[r] > 0xFFFFFFFFull) return fail(c, KH_ERR_BAD_ARG, "kh_unitigs_paths: a record of 2^32 or more window starts");
-    }
-    if (nrec && rec_start[nrec] > n) return fail(c, KH_ERR_BAD_ARG, "kh_unitigs_paths: rec_start[nrec] is beyond n");
+    // (after enter(), unlike kh_profile_records: a poisoned context reports that before a bad rec_start)
+    if ((rc = check_rec_start(c, who, reinterpret_cast<const u64 *>(rec_start), nrec, n)) != KH_OK) return rc;
     *n_runs = 0;
     if (nrec == 0) return KH_OK;
     if (n == 0) {
         memset(run_start, 0, (nrec + 1) * sizeof(u64));
         return KH_OK;
     }
-    const bool with_qual = qual != nullptr && c->minq >= 0;
     const u64 chunk = profile_chunk(c, n), nch = (n + chunk - 1) / chunk;
     const u64 nu = c->un.n_unitigs;
     // (the staging and the call's arrays first: whichever allocation fails, nothing of the place map stays behind)
@@ -516,28 +489,12 @@ extern "C" int kh_unitigs_paths(kh_ctx *c, const uint8_t *bases, const uint8_t *
     if (d_cover && nu) HIP_TRY(c, hipMemsetAsync(d_cover, 0, nu * KH_COV_WORDS * sizeof(u64), c->stream));
     PathTimes times(c);
     const PathCall pc{n, nrec, run_cap, d_rec, d_run_start, d_runs, &times};
-    // The bases travel as in kh_unitigs_locate: chunk j owns the window starts [j chunk, (j + 1) chunk) and is sent the bytes they need,
-    // from the window start in front of its first; nothing of it comes back.
-    const bool in_direct = is_pinned_host(bases) && (!with_qual || is_pinned_host(qual));
-    const u64 stride = pf_in_stride(c->pf_chunk), k1 = c->k - 1;
-    for (u64 j = 0; j < nch; ++j) {
-        // (the buffers of chunk j were those of chunk j - 2, whose kernels the last round saw complete)
-        const int b = (int)(j & 1);
-        const u64 a = j * chunk, ns = std::min<u64>(chunk, n - a), from = a - (a ? 1 : 0);
-        const u64 len = std::min<u64>(a + ns + 1 + k1, n) - from;
-        uint8_t *const d = c->pf_d[b], *const h = c->pf_h[b];
-        if (!in_direct) {
-            staged_memcpy(h, bases + from, len);
-            if (with_qual) staged_memcpy(h + stride, qual + from, len);
-        }
-        HIP_TRY(c, hipMemcpyAsync(d, in_direct ? bases + from : h, len, hipMemcpyHostToDevice, c->cstream));
-        if (with_qual) HIP_TRY(c, hipMemcpyAsync(d + stride, in_direct ? qual + from : h + stride, len, hipMemcpyHostToDevice, c->cstream));
-        HIP_TRY(c, hipEventRecord(c->pf_in[b], c->cstream));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pf_in[b], 0));
-        if ((rc = path_chunk(c, pc, ps, j, a, ns, d, with_qual ? d + stride : nullptr, len, reinterpret_cast<u64 *>(d + 2 * stride))) != KH_OK) return rc;
-        HIP_TRY(c, hipEventRecord(c->pf_run[b], c->stream));
-        if (j) HIP_TRY(c, hipEventSynchronize(c->pf_run[b ^ 1]));
-    }
+    // The bases travel as in kh_unitigs_locate, from the window start in front of a chunk's first to the one behind its last (the halo);
+    // nothing of a chunk comes back, and its words lie where kh_unitigs_locate's would.
+    rc = chunk_pipeline(c, bases, qual, n, chunk, 1, nullptr, 0, [&](const ChunkJob &job) {
+        return path_chunk(c, pc, ps, job.j, job.a, job.ns, job.d_bases, job.d_qual, job.len, reinterpret_cast<u64 *>(job.d_tail));
+    });
+    if (rc != KH_OK) return rc;
     u64 total = 0;
     if ((rc = path_total(c, ps, nch, &total)) != KH_OK) return rc;
     *n_runs = total;

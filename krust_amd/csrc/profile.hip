@@ -258,20 +258,7 @@ __global__ __launch_bounds__(BLOCK) void profile_records_kernel(const uint8_t *_
         const u64 Gs = (u64)(G0 + e_lo), Ge = (u64)(G0 + e_hi);
 
         if (!searched) {  // the first record that ends behind Gs (r_hi: none)
-            u64 a = r_lo, b = r_hi;
-            while (a < b) {
-                const u64 step = (b - a + BLOCK - 1) / BLOCK;
-                const u64 idx = a + (u64)tid * step;
-                const int c = __syncthreads_count(idx < b && rec_start[idx + 1] <= Gs);
-                if (c == 0) {
-                    b = a;
-                } else {
-                    const u64 nb = a + (u64)c * step;
-                    a = a + (u64)(c - 1) * step + 1;
-                    if (nb < b) b = nb;
-                }
-            }
-            rcur = a;
+            rcur = wg_first_not(r_lo, r_hi, tid, [&](u64 r) { return rec_start[r + 1] <= Gs; });
             searched = true;
         }
 
@@ -346,7 +333,7 @@ namespace khi {
 constexpr u64 PF_CHUNK_MAX = 4ull << 20;   // window starts per chunk of kh_profile: 4 MiB of bases in, 16 MiB of profile out
 constexpr u64 PF_CHUNK_MIN = 64ull << 10;
 
-// the chunk buffers and events of the two host forms (profile_buffers grows them by releasing them first)
+// the chunk buffers and events of the four host forms (profile_buffers grows them by releasing them first)
 static void chunk_release(kh_ctx *c) {
     for (int i = 0; i < 2; ++i) {
         if (c->pf_d[i]) (void)dev_free(c->pf_d[i]);
@@ -412,6 +399,79 @@ int profile_buffers(kh_ctx *c, u64 chunk, u64 out_bytes, const char *who) {
     return KH_OK;
 }
 
+int chunk_pipeline(kh_ctx *c, const uint8_t *bases, const uint8_t *qual, u64 n, u64 chunk, u64 halo, void *out, u64 out_bytes,
+                   const std::function<int(const ChunkJob &)> &launch) {
+    const bool with_qual = qual_filter(c, qual);
+    // pinned / registered caller memory: the copy engine reads and writes it itself, no bounce through pf_h
+    const bool in_direct = is_pinned_host(bases) && (!with_qual || is_pinned_host(qual));
+    const bool out_direct = out && is_pinned_host(out);
+    const u64 stride = pf_in_stride(c->pf_chunk), k1 = c->k - 1;  // (the buffers' real size, not this call's chunk)
+    const u64 nch = (n + chunk - 1) / chunk;
+    // Chunk j owns the window starts [j chunk, (j + 1) chunk).  A window is answered by the chunk that holds its start, so no entry
+    // of out is written twice.
+    auto finish = [&](u64 j) -> int {  // chunk j has arrived in pinned memory: out of the bounce buffer
+        const int b = (int)(j & 1);
+        HIP_TRY(c, hipEventSynchronize(c->pf_out[b]));
+        if (!out_direct) staged_memcpy((uint8_t *)out + out_bytes * j * chunk, c->pf_h[b] + 2 * stride, out_bytes * std::min(chunk, n - j * chunk));
+        return KH_OK;
+    };
+    for (u64 j = 0; j < nch; ++j) {
+        // The buffers of chunk j were those of chunk j - 2, which the last round saw complete: with out, finish() saw its results
+        // arrive; without, the host waited for its kernel.
+        const int b = (int)(j & 1);
+        const u64 a = j * chunk, ns = std::min(chunk, n - a), from = a - (halo && a ? 1 : 0);
+        const u64 len = std::min(a + ns + halo + k1, n) - from;
+        uint8_t *const d = c->pf_d[b], *const h = c->pf_h[b];
+        if (!in_direct) {
+            staged_memcpy(h, bases + from, len);
+            if (with_qual) staged_memcpy(h + stride, qual + from, len);
+        }
+        HIP_TRY(c, hipMemcpyAsync(d, in_direct ? bases + from : h, len, hipMemcpyHostToDevice, c->cstream));
+        if (with_qual) HIP_TRY(c, hipMemcpyAsync(d + stride, in_direct ? qual + from : h + stride, len, hipMemcpyHostToDevice, c->cstream));
+        HIP_TRY(c, hipEventRecord(c->pf_in[b], c->cstream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pf_in[b], 0));
+        int rc = launch(ChunkJob{j, a, ns, d, with_qual ? d + stride : nullptr, len, d + 2 * stride});
+        if (rc != KH_OK) return rc;
+        HIP_TRY(c, hipEventRecord(c->pf_run[b], c->stream));
+        if (!out) {
+            if (j) HIP_TRY(c, hipEventSynchronize(c->pf_run[b ^ 1]));
+            continue;
+        }
+        // the results of chunk j travel on a stream of their own, beside the kernel of chunk j + 1
+        HIP_TRY(c, hipStreamWaitEvent(c->cstream2, c->pf_run[b], 0));
+        HIP_TRY(c, hipMemcpyAsync(out_direct ? (uint8_t *)out + out_bytes * a : h + 2 * stride, d + 2 * stride, out_bytes * ns, hipMemcpyDeviceToHost,
+                                  c->cstream2));
+        HIP_TRY(c, hipEventRecord(c->pf_out[b], c->cstream2));
+        if (j && (rc = finish(j - 1)) != KH_OK) return rc;
+    }
+    return out ? finish(nch - 1) : KH_OK;
+}
+
+ReadPlan read_plan(const kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 n, u64 nout) {
+    ReadPlan p;
+    const u64 lead = (uintptr_t)d_bases & 15;
+    p.abase = d_bases - lead;
+    p.vbeg = lead, p.vend = lead + n;
+    const bool use_qual = qual_filter(c, d_qual, &p.thr);
+    p.qbase = use_qual ? d_qual - lead : nullptr;  // same virtual coordinates as the bases
+    p.qaligned = use_qual && (((uintptr_t)p.qbase) & 15) == 0;
+    p.ntiles = (p.vbeg + (c->k - 1) + nout + kh::TILE - 1) / kh::TILE;
+    u64 blocks = p.ntiles < (u64)grid_cap() ? p.ntiles : (u64)grid_cap();
+    p.tpb = (uint32_t)((p.ntiles + blocks - 1) / blocks);
+    p.blocks = (unsigned)((p.ntiles + p.tpb - 1) / p.tpb);
+    return p;
+}
+
+int check_rec_start(kh_ctx *c, const char *who, const u64 *rec_start, u64 nrec, u64 n) {
+    const std::string w(who);
+    for (u64 r = 0; r < nrec; ++r) {
+        if (rec_start[r] > rec_start[r + 1]) return fail(c, KH_ERR_BAD_ARG, (w + ": rec_start is not ascending").c_str());
+        if (rec_start[r + 1] - rec_start[r] > 0xFFFFFFFFull) return fail(c, KH_ERR_BAD_ARG, (w + ": a record of 2^32 or more window starts").c_str());
+    }
+    if (nrec && rec_start[nrec] > n) return fail(c, KH_ERR_BAD_ARG, (w + ": rec_start[nrec] is beyond n").c_str());
+    return KH_OK;
+}
+
 namespace {
 
 // What profile_records_kernel needs beyond profile_kernel's arguments (see there).
@@ -429,38 +489,22 @@ int pr_sum_word(const uint32_t *d_rows) { return (((uintptr_t)d_rows) & 7) == 4 
 // them; asynchronous on the compute stream.
 int profile_range(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, u64 n, u64 nout, uint32_t *d_out, const RecArgs *rec = nullptr) {
     if (nout == 0) return KH_OK;
-    const u64 lead = (uintptr_t)d_bases & 15;
-    const uint8_t *abase = d_bases - lead;
-    const u64 vbeg = lead, vend = lead + n;
-    const bool use_qual = d_qual != nullptr && c->minq >= 0;
-    const uint8_t *qbase = use_qual ? d_qual - lead : nullptr;  // same virtual coordinates as the bases
-    const int qaligned = use_qual && (((uintptr_t)qbase) & 15) == 0;
-    uint32_t thr = 0;
-    if (use_qual) {
-        const int t = c->minq + 33;  // saturating_add(33) on u8, run.rs:538
-        thr = (uint32_t)(t > 255 ? 255 : t);
-    }
-    // the window that starts at entry i ends at position vbeg + i + k - 1
-    const u64 ntiles = (vbeg + (c->k - 1) + nout + kh::TILE - 1) / kh::TILE;
-    u64 blocks = ntiles < (u64)grid_cap() ? ntiles : (u64)grid_cap();
-    const uint32_t tpb = (uint32_t)((ntiles + blocks - 1) / blocks);  // contiguous tiles per workgroup: the look-back is carried in LDS
-    blocks = (ntiles + tpb - 1) / tpb;
+    const ReadPlan p = read_plan(c, d_bases, d_qual, n, nout);
+    const dim3 grid(p.blocks), block(kh::BLOCK);
     with_probe(c, [&](auto tab) {
         typedef decltype(tab) TAB;
-        if (rec && use_qual)
-            hipLaunchKernelGGL((kh::profile_records_kernel<true, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase, qbase, qaligned,
-                               vbeg, vend, ntiles, tpb, c->k, thr, tab, nout, rec->d_rec_start, rec->r_lo, rec->r_hi, rec->out0, rec->lo, rec->hi,
-                               rec->d_rows, rec->sumw);
+        if (rec && p.qbase)
+            hipLaunchKernelGGL((kh::profile_records_kernel<true, TAB>), grid, block, 0, c->stream, p.abase, p.qbase, p.qaligned, p.vbeg, p.vend, p.ntiles,
+                               p.tpb, c->k, p.thr, tab, nout, rec->d_rec_start, rec->r_lo, rec->r_hi, rec->out0, rec->lo, rec->hi, rec->d_rows, rec->sumw);
         else if (rec)
-            hipLaunchKernelGGL((kh::profile_records_kernel<false, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase,
-                               (const uint8_t *)nullptr, 0, vbeg, vend, ntiles, tpb, c->k, 0u, tab, nout, rec->d_rec_start, rec->r_lo, rec->r_hi,
-                               rec->out0, rec->lo, rec->hi, rec->d_rows, rec->sumw);
-        else if (use_qual)
-            hipLaunchKernelGGL((kh::profile_kernel<true, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase, qbase, qaligned, vbeg,
-                               vend, ntiles, tpb, c->k, thr, tab, d_out, nout);
+            hipLaunchKernelGGL((kh::profile_records_kernel<false, TAB>), grid, block, 0, c->stream, p.abase, p.qbase, p.qaligned, p.vbeg, p.vend, p.ntiles,
+                               p.tpb, c->k, p.thr, tab, nout, rec->d_rec_start, rec->r_lo, rec->r_hi, rec->out0, rec->lo, rec->hi, rec->d_rows, rec->sumw);
+        else if (p.qbase)
+            hipLaunchKernelGGL((kh::profile_kernel<true, TAB>), grid, block, 0, c->stream, p.abase, p.qbase, p.qaligned, p.vbeg, p.vend, p.ntiles, p.tpb,
+                               c->k, p.thr, tab, d_out, nout);
         else
-            hipLaunchKernelGGL((kh::profile_kernel<false, TAB>), dim3((unsigned)blocks), dim3(kh::BLOCK), 0, c->stream, abase,
-                               (const uint8_t *)nullptr, 0, vbeg, vend, ntiles, tpb, c->k, 0u, tab, d_out, nout);
+            hipLaunchKernelGGL((kh::profile_kernel<false, TAB>), grid, block, 0, c->stream, p.abase, p.qbase, p.qaligned, p.vbeg, p.vend, p.ntiles, p.tpb,
+                               c->k, p.thr, tab, d_out, nout);
     });
     HIP_TRY(c, hipGetLastError());
     return KH_OK;
@@ -525,46 +569,11 @@ extern "C" int kh_profile(kh_ctx *c, const uint8_t *bases, const uint8_t *qual, 
     int rc = enter(c, ENTER_READ);
     if (rc != KH_OK) return rc;
     if (n == 0) return KH_OK;
-    const bool with_qual = qual != nullptr && c->minq >= 0;
     const u64 chunk = profile_chunk(c, n);
     if ((rc = profile_buffers(c, chunk)) != KH_OK) return rc;
-    // pinned / registered caller memory: the copy engine reads and writes it itself, no bounce through pf_h
-    const bool in_direct = is_pinned_host(bases) && (!with_qual || is_pinned_host(qual));
-    const bool out_direct = is_pinned_host(out);
-    const u64 stride = pf_in_stride(c->pf_chunk), k1 = c->k - 1;
-    const u64 nch = (n + chunk - 1) / chunk;
-    // Chunk j owns the window starts [j chunk, (j + 1) chunk) and is sent the bytes they need: its own and the k - 1 after them
-    // (the overlap).  A window is answered by the chunk that holds its start, so no entry of out is written twice.
-    auto starts = [&](u64 j) { return std::min(chunk, n - j * chunk); };
-    auto finish = [&](u64 j) -> int {  // chunk j has arrived in pinned memory: out of the bounce buffer
-        const int b = (int)(j & 1);
-        HIP_TRY(c, hipEventSynchronize(c->pf_out[b]));
-        if (!out_direct) staged_memcpy(out + j * chunk, c->pf_h[b] + 2 * stride, 4 * starts(j));
-        return KH_OK;
-    };
-    for (u64 j = 0; j < nch; ++j) {
-        // (the buffers of chunk j were those of chunk j - 2, which finish() saw complete in the last round)
-        const int b = (int)(j & 1);
-        const u64 a = j * chunk, ns = starts(j), len = std::min(ns + k1, n - a);
-        uint8_t *const d = c->pf_d[b], *const h = c->pf_h[b];
-        if (!in_direct) {
-            staged_memcpy(h, bases + a, len);
-            if (with_qual) staged_memcpy(h + stride, qual + a, len);
-        }
-        HIP_TRY(c, hipMemcpyAsync(d, in_direct ? bases + a : h, len, hipMemcpyHostToDevice, c->cstream));
-        if (with_qual) HIP_TRY(c, hipMemcpyAsync(d + stride, in_direct ? qual + a : h + stride, len, hipMemcpyHostToDevice, c->cstream));
-        HIP_TRY(c, hipEventRecord(c->pf_in[b], c->cstream));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pf_in[b], 0));
-        uint32_t *const d_out = reinterpret_cast<uint32_t *>(d + 2 * stride);
-        if ((rc = profile_range(c, d, with_qual ? d + stride : nullptr, len, ns, d_out)) != KH_OK) return rc;
-        HIP_TRY(c, hipEventRecord(c->pf_run[b], c->stream));
-        // the profile of chunk j travels on a stream of its own, beside the kernel of chunk j + 1
-        HIP_TRY(c, hipStreamWaitEvent(c->cstream2, c->pf_run[b], 0));
-        HIP_TRY(c, hipMemcpyAsync(out_direct ? (void *)(out + a) : (void *)(h + 2 * stride), d_out, 4 * ns, hipMemcpyDeviceToHost, c->cstream2));
-        HIP_TRY(c, hipEventRecord(c->pf_out[b], c->cstream2));
-        if (j && (rc = finish(j - 1)) != KH_OK) return rc;
-    }
-    return finish(nch - 1);
+    return chunk_pipeline(c, bases, qual, n, chunk, 0, out, sizeof(uint32_t), [&](const ChunkJob &job) {
+        return profile_range(c, job.d_bases, job.d_qual, job.len, job.ns, reinterpret_cast<uint32_t *>(job.d_tail));
+    });
 }
 
 extern "C" int kh_profile_records_device(kh_ctx *c, const uint8_t *d_bases, const uint8_t *d_qual, uint64_t n, const uint64_t *d_rec_start,
@@ -593,13 +602,9 @@ extern "C" int kh_profile_records(kh_ctx *c, const uint8_t *bases, const uint8_t
     if ((n && !bases) || (nrec && (!rec_start || !rows))) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records: NULL argument");
     if ((uintptr_t)rows & 3) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records: rows is not 4-byte aligned");
     if ((uintptr_t)rec_start & 7) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records: rec_start is not 8-byte aligned");
-    for (u64 r = 0; r < nrec; ++r) {
-        if (rec_start[r] > rec_start[r + 1]) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records: rec_start is not ascending");
-        if (rec_start[r + 1] - rec_start[r] > 0xFFFFFFFFull) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records: a record of 2^32 or more window starts");
-    }
-    if (nrec && rec_start[nrec] > n) return fail(c, KH_ERR_BAD_ARG, "kh_profile_records: rec_start[nrec] is beyond n");
-    int rc = enter(c, ENTER_READ);
+    int rc = check_rec_start(c, "kh_profile_records", reinterpret_cast<const u64 *>(rec_start), nrec, n);  // (before enter(): see kh_unitigs_paths)
     if (rc != KH_OK) return rc;
+    if ((rc = enter(c, ENTER_READ)) != KH_OK) return rc;
     if (nrec == 0) return KH_OK;
     if ((rc = records_buffers(c, nrec)) != KH_OK) return rc;
     uint32_t *const d_rows = c->pr_rows;
@@ -607,36 +612,18 @@ extern "C" int kh_profile_records(kh_ctx *c, const uint8_t *bases, const uint8_t
     HIP_TRY(c, hipMemcpyAsync(c->pr_rec, rec_start, (nrec + 1) * sizeof(u64), hipMemcpyHostToDevice, c->stream));
     if ((rc = records_preset(c, d_rows, nrec, sumw)) != KH_OK) return rc;
     if (n) {
-        const bool with_qual = qual != nullptr && c->minq >= 0;
         const u64 chunk = profile_chunk(c, n);
         if ((rc = profile_buffers(c, chunk)) != KH_OK) return rc;
-        const bool in_direct = is_pinned_host(bases) && (!with_qual || is_pinned_host(qual));
-        const u64 stride = pf_in_stride(c->pf_chunk), k1 = c->k - 1;
-        const u64 nch = (n + chunk - 1) / chunk;
-        // Chunk j owns the window starts [j chunk, (j + 1) chunk), as in kh_profile; nothing of it comes back: its kernel adds to the rows.
-        for (u64 j = 0; j < nch; ++j) {
-            // (the buffers of chunk j were those of chunk j - 2, whose kernel the last round saw complete)
-            const int b = (int)(j & 1);
-            const u64 a = j * chunk, ns = std::min(chunk, n - a), len = std::min(ns + k1, n - a);
-            uint8_t *const d = c->pf_d[b], *const h = c->pf_h[b];
-            if (!in_direct) {
-                staged_memcpy(h, bases + a, len);
-                if (with_qual) staged_memcpy(h + stride, qual + a, len);
-            }
-            HIP_TRY(c, hipMemcpyAsync(d, in_direct ? bases + a : h, len, hipMemcpyHostToDevice, c->cstream));
-            if (with_qual) HIP_TRY(c, hipMemcpyAsync(d + stride, in_direct ? qual + a : h + stride, len, hipMemcpyHostToDevice, c->cstream));
-            HIP_TRY(c, hipEventRecord(c->pf_in[b], c->cstream));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pf_in[b], 0));
-            // the records that own a window start of this chunk: those that end behind a and start before a + ns
-            const u64 r_lo = (u64)(std::upper_bound(rec_start + 1, rec_start + nrec + 1, a) - (rec_start + 1));
-            const u64 r_hi = (u64)(std::lower_bound(rec_start, rec_start + nrec, a + ns) - rec_start);
-            if (r_lo < r_hi) {
-                const RecArgs ra{c->pr_rec, r_lo, r_hi, a, lo, hi, d_rows, sumw};
-                if ((rc = profile_range(c, d, with_qual ? d + stride : nullptr, len, ns, nullptr, &ra)) != KH_OK) return rc;
-            }
-            HIP_TRY(c, hipEventRecord(c->pf_run[b], c->stream));
-            if (j) HIP_TRY(c, hipEventSynchronize(c->pf_run[b ^ 1]));
-        }
+        // nothing of a chunk comes back: its kernel adds to the rows
+        rc = chunk_pipeline(c, bases, qual, n, chunk, 0, nullptr, 0, [&](const ChunkJob &job) {
+            // the records that own a window start of this chunk: those that end behind a and start before a + ns (none: no launch)
+            const u64 r_lo = (u64)(std::upper_bound(rec_start + 1, rec_start + nrec + 1, job.a) - (rec_start + 1));
+            const u64 r_hi = (u64)(std::lower_bound(rec_start, rec_start + nrec, job.a + job.ns) - rec_start);
+            if (r_lo >= r_hi) return (int)KH_OK;
+            const RecArgs ra{c->pr_rec, r_lo, r_hi, job.a, lo, hi, d_rows, sumw};
+            return profile_range(c, job.d_bases, job.d_qual, job.len, job.ns, nullptr, &ra);
+        });
+        if (rc != KH_OK) return rc;
     }
     if ((rc = records_finalize(c, d_rows, nrec, sumw)) != KH_OK) return rc;
     return d2h_staged(c, rows, d_rows, nrec * KH_REC_WORDS * sizeof(uint32_t));  // the rows come back once
