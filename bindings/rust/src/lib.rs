@@ -140,6 +140,12 @@ pub mod sys {
                                        d_run_start: *mut u64, d_runs: *mut u32, run_cap: u64, d_cover: *mut u64, n_runs: *mut u64) -> c_int;
         pub fn kh_unitigs_paths(ctx: *mut KhCtx, bases: *const u8, qual: *const u8, n: u64, rec_start: *const u64, nrec: u64,
                                 run_start: *mut u64, runs: *mut u32, run_cap: u64, cover: *mut u64, n_runs: *mut u64) -> c_int;
+        /// how many records walk every link: two consecutive rows of a record with QEND == the next QSTART are a crossing, and
+        /// `support[l] += 1` if its word is link l (`cap` >= n_links counters, added to); `out` (may be null) takes the 4 words KH_SUP_*
+        pub fn kh_unitigs_link_support_device(ctx: *mut KhCtx, d_run_start: *const u64, nrec: u64, d_runs: *const u32, n_runs: u64,
+                                              d_support: *mut u64, cap: u64, out: *mut u64) -> c_int;
+        pub fn kh_unitigs_link_support(ctx: *mut KhCtx, run_start: *const u64, nrec: u64, runs: *const u32, n_runs: u64,
+                                       support: *mut u64, cap: u64, out: *mut u64) -> c_int;
         /// one round of tip clipping of `src`'s compacted graph at `min_count`: the k-mers of the surviving unitigs are added to `dst`
         /// (`count[key] += c`); `out` takes the 8 words KH_CLIP_* of the header names
         pub fn kh_clip_tips_into(dst: *mut KhCtx, src: *mut KhCtx, min_count: u64, max_kmers: u64, out: *mut u64) -> c_int;
@@ -266,6 +272,15 @@ pub const RUN_QEND: usize = 3;
 pub const COV_WORDS: usize = 2;
 pub const COV_WINDOWS: usize = 0;
 pub const COV_RUNS: usize = 1;
+/// `KH_SUP_WORDS`: the words of [`HipKmerMap::unitigs_link_support`] -- `SUP_PAIRS` (consecutive rows of one record), `SUP_ADJACENT`
+/// (of those: no window start between them), `SUP_CREDITED` (of those: the word is a link), `SUP_MISSING` (the rest).
+pub const SUP_WORDS: usize = 4;
+pub const SUP_PAIRS: usize = 0;
+pub const SUP_ADJACENT: usize = 1;
+pub const SUP_CREDITED: usize = 2;
+pub const SUP_MISSING: usize = 3;
+/// The mirror of a link word (a << 32) | b: the crossing that the reverse-complemented read makes.
+pub const fn link_mirror(w: u64) -> u64 { (((w & 0xFFFF_FFFF) ^ 1) << 32) | ((w >> 32) ^ 1) }
 /// `KH_UNI_LINK_FROM(w)`: the unitig a link word of `kh_unitigs_links_copy` leaves (a row index of `kh_unitigs_copy`).
 pub const fn uni_link_from(w: u64) -> u32 { (w >> 33) as u32 }
 /// `KH_UNI_LINK_FROM_SIGN(w)`: 0 = it leaves the right end of the reported sequence (+), 1 = that of its reverse complement (-).
@@ -741,6 +756,55 @@ impl HipKmerMap {
         err?;
         check(self.ctx, end)?;
         Ok((run_start, runs, cover))
+    }
+
+    /// How many records of `bases` walk every link between the unitigs of the table at `min_count` (`kh_unitigs_begin_linked` /
+    /// `kh_unitigs_paths` twice / `kh_unitigs_links_copy` / `kh_unitigs_link_support` / `kh_unitigs_end`).  Returns `(links, support,
+    /// stats)`: the link words, one counter per link in the same order, and the `SUP_WORDS` words of the call.  A read credits the
+    /// word as read; `support[l] + support[index of link_mirror(links[l])]` is the strand-free number.
+    pub fn unitigs_link_support(&self, min_count: u64, bases: &[u8], qual: Option<&[u8]>, rec_start: &[u64])
+                                -> Result<(Vec<u64>, Vec<u64>, [u64; SUP_WORDS]), HipError> {
+        if let Some(q) = qual {
+            if q.len() != bases.len() {
+                return Err(HipError::Device("qual must have the same length as bases".into()));
+            }
+        }
+        if rec_start.is_empty() {
+            return Err(HipError::Device("rec_start needs nrec + 1 offsets".into()));
+        }
+        let nrec = (rec_start.len() - 1) as u64;
+        let (mut nu, mut nb, mut nl) = (0u64, 0u64, 0u64);
+        check(self.ctx, unsafe { sys::kh_unitigs_begin_linked(self.ctx, min_count, &mut nu, &mut nb, &mut nl) })?;
+        let qp = qual.map_or(std::ptr::null(), |q| q.as_ptr());
+        let mut run_start = vec![0u64; rec_start.len()];
+        let mut total = 0u64;
+        let mut rc = unsafe {
+            sys::kh_unitigs_paths(self.ctx, bases.as_ptr(), qp, bases.len() as u64, rec_start.as_ptr(), nrec, run_start.as_mut_ptr(),
+                                  std::ptr::null_mut(), 0, std::ptr::null_mut(), &mut total)
+        };
+        let mut runs = vec![0u32; total as usize * RUN_WORDS];
+        if rc == -8 {  // KH_ERR_RANGE: there are runs -- now with room for them
+            rc = unsafe {
+                sys::kh_unitigs_paths(self.ctx, bases.as_ptr(), qp, bases.len() as u64, rec_start.as_ptr(), nrec, run_start.as_mut_ptr(),
+                                      runs.as_mut_ptr(), total, std::ptr::null_mut(), &mut total)
+            };
+        }
+        let mut links = vec![0u64; nl as usize];
+        let mut support = vec![0u64; nl as usize];
+        let mut stats = [0u64; SUP_WORDS];
+        if rc == 0 {
+            rc = unsafe { sys::kh_unitigs_links_copy(self.ctx, links.as_mut_ptr(), nl) };
+        }
+        if rc == 0 {
+            rc = unsafe {
+                sys::kh_unitigs_link_support(self.ctx, run_start.as_ptr(), nrec, runs.as_ptr(), total, support.as_mut_ptr(), nl, stats.as_mut_ptr())
+            };
+        }
+        let err = check(self.ctx, rc);  // (before kh_unitigs_end replaces the error text)
+        let end = unsafe { sys::kh_unitigs_end(self.ctx) };
+        err?;
+        check(self.ctx, end)?;
+        Ok((links, support, stats))
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

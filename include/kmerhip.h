@@ -69,7 +69,7 @@ typedef enum kh_status {
 /* Allocation failures: what KH_ERR_OOM leaves behind.  One rule per kind of call; the comments further down only add to it.
  *   - A READING call takes the table as it is and allocates only for itself: kh_result_size / _copy / _copy_device / _sorted*,
  *     kh_result_text_*, kh_histogram, kh_lookup, kh_profile*, kh_profile_records*, kh_compare, kh_graph_*, kh_unitigs_*,
- *     kh_unitigs_text_begin / kh_unitigs_text_next / kh_unitigs_text_next_device, kh_unitigs_paths / kh_unitigs_paths_device and the src side of kh_clip_tips_into / kh_pop_bubbles_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
+ *     kh_unitigs_text_begin / kh_unitigs_text_next / kh_unitigs_text_next_device, kh_unitigs_paths / kh_unitigs_paths_device, kh_unitigs_link_support / kh_unitigs_link_support_device and the src side of kh_clip_tips_into / kh_pop_bubbles_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
  *     allocation, the table is unchanged and the context is NOT poisoned: the same call can be made again.  What the call
  *     allocated is released, except the scratch the context keeps for the next such call where that had been allocated
  *     before the failure: the pinned staging chunks and the copy stream of the host forms, the scan scratch (not after the
@@ -620,6 +620,51 @@ int kh_unitigs_paths_device(kh_ctx *ctx, const uint8_t *d_bases, const uint8_t *
                             uint64_t nrec, uint64_t *d_run_start, uint32_t *d_runs, uint64_t run_cap, uint64_t *d_cover, uint64_t *n_runs);
 int kh_unitigs_paths(kh_ctx *ctx, const uint8_t *bases, const uint8_t *qual, uint64_t n, const uint64_t *rec_start,
                      uint64_t nrec, uint64_t *run_start, uint32_t *runs, uint64_t run_cap, uint64_t *cover, uint64_t *n_runs);
+
+/* ---- READ SUPPORT PER LINK: how many records walk from one unitig end into another (edge weights, the RC:i: tag of an L line) -- */
+/* cover tells how much read evidence lies on a node of the compacted graph; these calls tell it for an edge.  They need the live
+ * unitigs of kh_unitigs_begin_linked and count, on the device, the link crossings of run rows.
+ * INPUT: run_start and runs are what a kh_unitigs_paths* call wrote: run_start has nrec + 1 CSR entries with run_start[nrec] ==
+ *   n_runs, runs has n_runs rows of KH_RUN_WORDS words.  The rows need not come from this library: only the lookup below is defined
+ *   on them.  Rows in front of run_start[0] belong to no record.
+ * CROSSING: rows i and i + 1 form a crossing if both belong to the same record and QEND of row i == QSTART of row i + 1.  The last
+ *   row of a record never pairs with the first row of the next, whatever their QSTART / QEND.  The WORD of a crossing is
+ *   (STATE_i << 32) | STATE_{i+1}: a run stays in one unitig in one direction, so its STATE is both the end state it leaves through
+ *   and the state it was entered with -- the encoding of a link word.  If the word is link number l of kh_unitigs_links_copy,
+ *   support[l] += 1; otherwise the crossing counts as KH_SUP_MISSING and nothing is stored for it.  The closing link of a circular
+ *   unitig and every turn of a homopolymer loop are crossings.
+ * OUTPUT: support has n_links 64-bit counters in link-array order; they wrap modulo 2^64.  Counts are ADDED: a caller streams
+ *   batches into one array, as with cover.  Device memory in the device form, host memory in the host form.  cap < n_links is
+ *   KH_ERR_RANGE with nothing written; a NULL support with cap == 0 is allowed only when n_links == 0.  out (host memory in both
+ *   forms, may be NULL) gets the KH_SUP_WORDS words of THIS call, not added.  On anything but KH_OK, support and out are untouched.
+ * STRANDS: a crossing credits the word as read.  The same read reverse-complemented credits the mirror word
+ *   ((b ^ 1) << 32) | (a ^ 1) of (a << 32) | b, which is in the list too; support[l] + support[mirror(l)] is the strand-free
+ *   number and is the caller's arithmetic.  (The sign of a palindromic unitig counts as either: see WHAT FOLLOWS of the links.  A
+ *   link into or out of one may be its own mirror, or mirror a word that differs from it in that sign only.)
+ * ENTRY: both enter as readers, like kh_unitigs_paths*: kh_stats, the table and a running kh_result_text_* or kh_unitigs_text_*
+ *   stream are left alone.  They never touch the table or the place map and do not build the place map.  KH_ERR_STATE without live
+ *   unitigs, and after a plain kh_unitigs_begin, which built no links (the message names kh_unitigs_begin_linked).
+ * KH_ERR_BAD_ARG (the context stays usable): NULL run_start or runs with n_runs > 0; NULL run_start with nrec > 0; NULL support with
+ *   cap > 0; runs not 4-byte aligned; run_start or support not 8-byte aligned.  In the host form only: run_start not ascending, or
+ *   run_start[nrec] != n_runs -- for the device form these two are the caller's contract: offsets or rows that break it give
+ *   unspecified credits and never an access outside runs[0 .. n_runs), support[0 .. n_links) or the library's own arrays.  A STATE of
+ *   2 * n_unitigs or more is simply KH_SUP_MISSING.
+ * n_runs < 2 or nrec == 0: KH_OK, out all zero, nothing else written.
+ * THE LINK INDEX: the first call after a kh_unitigs_begin_linked builds it, one uint64 per end state and KH_SUP_WORDS more
+ *   ((2 * n_unitigs + KH_SUP_WORDS) * 8 bytes of device memory of the context's own).  It lives and dies with the unitigs:
+ *   kh_unitigs_end, the next begin, kh_reset, kh_destroy; a begin that never asks for support allocates nothing for it.  KH_ERR_OOM
+ *   follows the rule of the reading calls: the context is not poisoned, the unitigs stay live, nothing of the index or of the call
+ *   stays allocated beyond what that rule lets a context keep (the pinned staging of the host form), and the next call tries again.
+ *   Later calls of kh_unitigs_link_support_device allocate nothing. */
+#define KH_SUP_WORDS 4
+#define KH_SUP_PAIRS 0      /* consecutive rows i, i+1 that belong to one record */
+#define KH_SUP_ADJACENT 1   /* of those: QEND of row i == QSTART of row i+1 (no window start between them) */
+#define KH_SUP_CREDITED 2   /* of those: (STATE_i << 32) | STATE_{i+1} is a link word; support[its index] += 1 */
+#define KH_SUP_MISSING 3    /* ADJACENT - CREDITED: 0 for rows that kh_unitigs_paths* wrote on these unitigs */
+int kh_unitigs_link_support_device(kh_ctx *ctx, const uint64_t *d_run_start, uint64_t nrec, const uint32_t *d_runs, uint64_t n_runs,
+                                   uint64_t *d_support, uint64_t cap, uint64_t *out /* KH_SUP_WORDS, host, may be NULL */);
+int kh_unitigs_link_support(kh_ctx *ctx, const uint64_t *run_start, uint64_t nrec, const uint32_t *runs, uint64_t n_runs,
+                            uint64_t *support, uint64_t cap, uint64_t *out);
 
 /* ---- tip clipping: one round of removing short dead-end branches (what assemblers do first with the compacted graph) --- */
 /* Take the unitigs and links of kh_unitigs_begin_linked(src, min_count): rows, end states (i, +) and (i, -) and link words exactly

@@ -13,6 +13,7 @@
 //   unitig_text.hip  kh_unitigs_text_*: those unitigs and links as FASTA / GFA text, formatted on the device and streamed out in pieces
 //   locate.hip    kh_unitigs_locate*: where on those unitigs the k-mer of every window start of new sequences lies (the place map)
 //   paths.hip     kh_unitigs_paths*: those places folded per record into runs along one unitig, and the coverage per unitig
+//   support.hip   kh_unitigs_link_support*: how many of those records walk every link between the unitigs (the link index)
 //   sort.hip      kh_result_sorted*: the result pairs in ascending key order (a device radix sort; format.hip streams it as text)
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
@@ -412,6 +413,10 @@ struct kh_ctx {
         // kh_unitigs_locate* (locate.hip): the place map, one word per table slot -- (2 u + o) << 32 | j for the node in that slot, all ones
         // for a slot that holds no node of S.  Built by the first locate call after a begin (cap * 8 bytes), released by unitigs_release().
         u64 *where = nullptr;
+        // kh_unitigs_link_support* (support.hip): the link index, one word per end state -- the index of the first link out of it, all ones
+        // for a state without links -- and behind them the KH_SUP_WORDS words the kernel adds up.  Built by the first support call after a
+        // kh_unitigs_begin_linked ((2 * n_unitigs + KH_SUP_WORDS) * 8 bytes), released by unitigs_release().
+        u64 *link_first = nullptr;
         // kh_unitigs_text_* (unitig_text.hip): these unitigs as text.  begin sizes every record and link line and scans both; next formats
         // ranges of whole tiles of UT_TILE bytes into one of two device chunks of the stream's OWN -- never the partition buffers: a
         // kh_result_text_* stream may run beside it -- and hands their bytes out: chunk i + 1 is formatted on `stream` while chunk i
@@ -570,6 +575,8 @@ int flush_acc(kh_ctx *c, bool carry);
 int flush_text(kh_ctx *c);
 int scan_unscanned(kh_ctx *c);
 bool is_pinned_host(const void *p);
+// The copy stream and, for need > 0, the two pinned staging buffers of 2 * stage_bytes each; soft: a reading call's KH_ERR_OOM.
+int ensure_stage(kh_ctx *c, u64 need, bool soft);
 void staged_memcpy(void *dst, const void *src, size_t n);  // several threads for a large copy
 // ready: the event behind which d_src is complete (nullptr: it was produced on the compute stream, which is then drained)
 int d2h_staged(kh_ctx *c, void *dst, const void *d_src, u64 bytes, hipEvent_t ready = nullptr);

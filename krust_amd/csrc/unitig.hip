@@ -683,6 +683,7 @@ void unitigs_release(kh_ctx *c) {
     if (c->un.bases) (void)dev_free(c->un.bases);
     if (c->un.links) (void)dev_free(c->un.links);
     if (c->un.where) (void)dev_free(c->un.where);  // (the place map of kh_unitigs_locate*, locate.hip)
+    if (c->un.link_first) (void)dev_free(c->un.link_first);  // (the link index of kh_unitigs_link_support*, support.hip)
     c->un = kh_ctx::Unitigs();
 }
 

@@ -113,6 +113,18 @@ def loc_is_place(words):
 RUN_WORDS, RUN_STATE, RUN_OFFSET, RUN_QSTART, RUN_QEND = 4, 0, 1, 2, 3
 COV_WORDS, COV_WINDOWS, COV_RUNS = 2, 0, 1
 
+# KH_SUP_*: the words of kh_unitigs_link_support* -- pairs of consecutive rows of one record, those without a window start between
+# them, those whose word is a link (credited), and the rest
+SUP_WORDS, SUP_PAIRS, SUP_ADJACENT, SUP_CREDITED, SUP_MISSING = 4, 0, 1, 2, 3
+SUP_NAMES = ("pairs", "adjacent", "credited", "missing")
+
+
+def link_mirror(words):
+    """The mirror of every link word (a << 32) | b: ((b ^ 1) << 32) | (a ^ 1) -- the crossing the reverse-complemented read makes."""
+    w = np.asarray(words, dtype=np.uint64)
+    one, lo = np.uint64(1), np.uint64(0xFFFFFFFF)
+    return (((w & lo) ^ one) << np.uint64(32)) | ((w >> np.uint64(32)) ^ one)
+
 # KH_CLIP_*: the words of kh_clip_tips_into
 CLIP_WORDS = 8
 CLIP_UNITIGS, CLIP_CANDIDATES, CLIP_CLIPPED, CLIP_CLIPPED_KMERS, CLIP_CLIPPED_COUNT, CLIP_KEPT_KMERS, CLIP_KEPT_COUNT, CLIP_LINKS = range(8)
@@ -206,6 +218,8 @@ SYMBOLS = {
     "kh_unitigs_locate": (C.c_int, [_P, _P, _P, _U64, _P]),
     "kh_unitigs_paths_device": (C.c_int, [_P, _P, _P, _U64, _P, _U64, _P, _P, _U64, _P, C.POINTER(_U64)]),
     "kh_unitigs_paths": (C.c_int, [_P, _P, _P, _U64, _P, _U64, _P, _P, _U64, _P, C.POINTER(_U64)]),
+    "kh_unitigs_link_support_device": (C.c_int, [_P, _P, _U64, _P, _U64, _P, _U64, _P]),
+    "kh_unitigs_link_support": (C.c_int, [_P, _P, _U64, _P, _U64, _P, _U64, _P]),
     "kh_clip_tips_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_pop_bubbles_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
@@ -697,6 +711,7 @@ class DeviceCounter:
         unitigs_copy* and unitigs_links_copy* fetch them, unitigs_end releases all of it."""
         nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         self._check(lib().kh_unitigs_begin_linked(self._h, int(min_count), C.byref(nu), C.byref(nb), C.byref(nl)))
+        self._n_links = int(nl.value)   # (what unitigs_link_support sizes a fresh array with)
         return int(nu.value), int(nb.value), int(nl.value)
 
     def unitigs_links_copy(self, n_links):
@@ -791,6 +806,38 @@ class DeviceCounter:
         if rc != KH_ERR_RANGE:
             self._check(rc)
         return rc, total.value
+
+    # -- read support per link -------------------------------------------------
+    def unitigs_link_support(self, run_start, runs, support=None):
+        """kh_unitigs_link_support: how many records walk every link of unitigs_begin_linked.  run_start and runs are what
+        unitigs_paths returned.  Two consecutive rows of a record with QEND == the next QSTART are a crossing; if its word
+        (STATE_i << 32) | STATE_i+1 is link number l of unitigs_links_copy, support[l] += 1.  support: a uint64 array of at least
+        n_links counters that the call ADDS to (a caller streams batches into it), or None for a fresh one of the n_links of this
+        object's last unitigs_begin_linked.  Returns (support, stats), stats a dict of this call's pairs, adjacent, credited and
+        missing (link_mirror gives the word the reverse-complemented read credits)."""
+        rs = np.ascontiguousarray(run_start, dtype=np.uint64)
+        rows = np.ascontiguousarray(runs, dtype=np.uint32).reshape(-1, RUN_WORDS)
+        if rs.ndim != 1 or rs.size < 1:
+            raise ValueError("run_start needs nrec + 1 offsets")
+        if support is None:
+            if getattr(self, "_n_links", None) is None:
+                raise ValueError("support=None needs the n_links of a unitigs_begin_linked made through this object")
+            support = np.zeros(self._n_links, dtype=np.uint64)
+        assert support.dtype == np.uint64 and support.ndim == 1 and support.flags.c_contiguous and support.flags.writeable
+        out = np.zeros(SUP_WORDS, dtype=np.uint64)
+        self._check(lib().kh_unitigs_link_support(self._h, rs.ctypes.data, rs.size - 1, rows.ctypes.data if rows.size else None, rows.shape[0],
+                                                  support.ctypes.data if support.size else None, support.size, out.ctypes.data))
+        return support, dict(zip(SUP_NAMES, (int(x) for x in out)))
+
+    def unitigs_link_support_device(self, d_run_start, nrec, d_runs, n_runs, d_support, cap):
+        """The same on device memory: integer addresses or torch tensors of nrec + 1 uint64 offsets and n_runs * 4 uint32 words (the
+        caller's contract, not checked: what unitigs_paths_device left there) and cap >= n_links uint64 counters to add to.  Returns
+        the stats dict when d_support is complete."""
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        out = np.zeros(SUP_WORDS, dtype=np.uint64)
+        self._check(lib().kh_unitigs_link_support_device(self._h, ptr(d_run_start), int(nrec), ptr(d_runs), int(n_runs), ptr(d_support), int(cap),
+                                                         out.ctypes.data))
+        return dict(zip(SUP_NAMES, (int(x) for x in out)))
 
     # -- tip clipping: one round over the compacted graph ---------------------
     def clip_tips_into(self, src, min_count=1, max_kmers=None):

@@ -44,6 +44,14 @@ With --paths, in ONE PROCESS PER SIZE, the same resident reads as run-compressed
   paths_pinned           kh_unitigs_paths from pinned memory into pinned arrays; locate_pinned = kh_unitigs_locate likewise, alternating
   split_ms               the device form's time on the device per step -- locate_range, path_flags_kernel, the scan, path_emit_kernel,
                          path_cover_kernel -- from HIP events round every launch (a second context with KH_FLAG_TRACE, one call)
+With --support, in ONE PROCESS PER SIZE, the read support per link (kh_unitigs_link_support*) on the rows the paths call left on the device:
+  paths_device           kh_unitigs_paths_device alone (no coverage array); paths_then_support = the same followed by
+                         kh_unitigs_link_support_device on its rows, the two alternating; support_over_paths = the difference of the medians
+                         over paths_device
+  crossings, links, links_without_support   ADJACENT of the call, n_links, and the share of links with support 0
+  split_ms               the traced split of one support call (the index build, link_support_kernel) and of the paths call before it
+                         (path_cover_kernel is the yardstick: one lane per row, atomics per row) -- a second context with KH_FLAG_TRACE
+  host_route             what the call replaces: the rows copied back, then np.searchsorted of the crossing words in the link array
 The measurement runs in a child process with a timeout; a failure is reported as {"error": ...}."""
 import argparse
 import json
@@ -411,7 +419,110 @@ def measure_paths_one(n, k):
     return out
 
 
+def measure_support_one(n, k):
+    import re
+    import tempfile
+    import numpy as np
+    import torch
+    from krust_amd import native
+    rl = 150
+    t = torch.empty(n * (rl + 1), dtype=torch.uint8, device="cuda:0")
+    native.synth_reads_device(t.data_ptr(), None, 20260130, 1 << 28, rl, 0, n, device=0)
+    torch.cuda.synchronize()
+    nrec = min(n, 1_000_000)
+    m = nrec * (rl + 1)                         # the reads that are walked: the first million of the table's own
+    d_in = t[:m]
+    rs = np.arange(0, m + 1, rl + 1, dtype=np.uint64)
+    d_rs = torch.from_numpy(rs.view(np.int64)).cuda()
+    d_st = torch.empty(nrec + 1, dtype=torch.int64, device="cuda:0")
+    out = {"k": k, "reads": n, "records": nrec, "window_starts": m}
+
+    def alternating(f, g, reps=5):
+        f(), g()
+        tf, tg = [], []
+        for _ in range(reps):
+            for fn, ts in ((f, tf), (g, tg)):
+                t0 = time.perf_counter()
+                fn()
+                ts.append(time.perf_counter() - t0)
+        tf.sort(), tg.sort()
+        return ({"median_s": tf[reps // 2], "spread_s": tf[-1] - tf[0]}, {"median_s": tg[reps // 2], "spread_s": tg[-1] - tg[0]})
+
+    def table(trace):
+        a = native.DeviceCounter(k, device=0, trace=trace)
+        a.push_device(t.data_ptr(), None, t.numel())
+        a.finish()
+        return a, a.unitigs_begin_linked(1)
+
+    a, (nu, nb, nl) = table(False)
+    rc, runs = a.unitigs_paths_device(d_in, None, m, d_rs, nrec, d_st, None, 0, None)      # sizes, and builds the place map
+    d_runs = torch.empty(max(runs, 1) * native.RUN_WORDS, dtype=torch.int32, device="cuda:0")
+    d_sup = torch.zeros(max(nl, 1), dtype=torch.int64, device="cuda:0")
+    d_cov = torch.zeros(nu * native.COV_WORDS, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    out.update(unitigs=nu, links=nl, runs=runs)
+    paths = lambda: a.unitigs_paths_device(d_in, None, m, d_rs, nrec, d_st, d_runs, runs, None)
+    stats = {}
+
+    def paths_then_support():
+        paths()
+        stats.update(a.unitigs_link_support_device(d_st, nrec, d_runs, runs, d_sup, nl))
+    alone, with_support = alternating(paths, paths_then_support)
+    out["paths_device"], out["paths_then_support"] = alone, with_support
+    out["support_s"] = with_support["median_s"] - alone["median_s"]
+    out["support_over_paths"] = out["support_s"] / alone["median_s"]
+    d_sup.zero_()
+    torch.cuda.synchronize()
+    stats = a.unitigs_link_support_device(d_st, nrec, d_runs, runs, d_sup, nl)
+    support = d_sup.cpu().numpy().view(np.uint64)[:nl]
+    out.update(stats=stats, crossings=stats["adjacent"], links_without_support=float(np.mean(support == 0)) if nl else 0.0)
+    assert stats["missing"] == 0 and int(support.sum()) == stats["credited"]
+
+    def host_route():                           # the rows copied back, the crossing words looked up in the link array on the CPU
+        run_start = d_st.cpu().numpy().view(np.uint64)
+        rows = d_runs.cpu().numpy().view(np.uint32).reshape(-1, native.RUN_WORDS)[:runs]
+        last = np.zeros(runs, dtype=bool)
+        last[run_start[1:][run_start[1:] > run_start[:-1]] - np.uint64(1)] = True          # the last row of every record that has one
+        pair = ~last[:-1] & (rows[:-1, native.RUN_QEND] == rows[1:, native.RUN_QSTART])
+        words = (rows[:-1, native.RUN_STATE].astype(np.uint64) << np.uint64(32)) | rows[1:, native.RUN_STATE].astype(np.uint64)
+        words = words[pair]
+        at = np.searchsorted(links, words)
+        hit = (at < nl) & (links[np.minimum(at, nl - 1)] == words)
+        return np.bincount(at[hit], minlength=nl).astype(np.uint64)
+    links = a.unitigs_links_copy(nl)
+    assert np.array_equal(host_route(), support)
+    out["host_route"] = timed(host_route)
+    a.unitigs_end()
+    a.close()
+    # the split: one traced call each of a second context, the lines read back from the process's stderr
+    b, _ = table(True)
+    b.unitigs_paths_device(d_in, None, m, d_rs, nrec, d_st, d_runs, runs, d_cov)           # (warm: builds the place map)
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            b.unitigs_paths_device(d_in, None, m, d_rs, nrec, d_st, d_runs, runs, d_cov)
+            b.unitigs_link_support_device(d_st, nrec, d_runs, runs, d_sup, nl)             # the first: builds the index
+            b.unitigs_link_support_device(d_st, nrec, d_runs, runs, d_sup, nl)
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        text = tmp.read().decode(errors="replace")
+    split = lambda l: {name: float(v) for name, v in re.findall(r"(\w+) ([0-9.]+) ms", l)}
+    sup = [l for l in text.splitlines() if "kh_unitigs_link_support_device:" in l]
+    pth = [l for l in text.splitlines() if "kh_unitigs_paths_device:" in l]
+    out["split_ms"] = ({"first": split(sup[0]), "later": split(sup[-1]), "paths": split(pth[-1])} if len(sup) == 2 and pth else {"error": text[-500:]})
+    b.unitigs_end()
+    b.close()
+    return out
+
+
 def measure(args):
+    if args.support:
+        print("RESULT " + json.dumps([measure_support_one(n, args.k) for n in args.reads]))
+        return
     if args.paths:
         print("RESULT " + json.dumps([measure_paths_one(n, args.k) for n in args.reads]))
         return
@@ -435,13 +546,14 @@ def main():
     ap.add_argument("--text", action="store_true", help="kh_unitigs_text_* beside kh_unitigs_begin_linked and the copies, one process per size")
     ap.add_argument("--locate", action="store_true", help="kh_unitigs_locate* beside kh_profile* and kh_unitigs_begin, one process per size")
     ap.add_argument("--paths", action="store_true", help="kh_unitigs_paths* beside kh_unitigs_locate* on the reads of --locate, one process per size")
+    ap.add_argument("--support", action="store_true", help="kh_unitigs_link_support_device behind kh_unitigs_paths_device on the reads of --paths, one process per size")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
         measure(args)
         return
-    if args.text or args.locate or args.paths:   # one process per size
-        which = "--paths" if args.paths else "--locate" if args.locate else "--text"
+    if args.text or args.locate or args.paths or args.support:   # one process per size
+        which = "--support" if args.support else "--paths" if args.paths else "--locate" if args.locate else "--text"
         res = []
         for n in args.reads:
             cmd = [sys.executable, os.path.abspath(__file__), "--child", which, "--k", str(args.k), "--reads", str(n)]
@@ -455,7 +567,7 @@ def main():
             except subprocess.TimeoutExpired:
                 res.append({"reads": n, "error": f"no result within {args.timeout} s"})
                 break
-        print(json.dumps({"probe": "unitig-paths" if args.paths else "unitig-locate" if args.locate else "unitig-text", "result": res}, indent=1))
+        print(json.dumps({"probe": "unitig-link-support" if args.support else "unitig-paths" if args.paths else "unitig-locate" if args.locate else "unitig-text", "result": res}, indent=1))
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k)] + (["--clip"] if args.clip else []) + (["--pop"] if args.pop else []) + ["--reads"] + [str(n) for n in args.reads]
     try:
