@@ -153,6 +153,13 @@ pub mod sys {
         /// places only the best stays, the k-mers of the surviving unitigs are added to `dst` (`count[key] += c`); `out` takes the 9
         /// words KH_POP_* of the header names
         pub fn kh_pop_bubbles_into(dst: *mut KhCtx, src: *mut KhCtx, min_count: u64, max_kmers: u64, out: *mut u64) -> c_int;
+        /// the connected components of the live unitigs of kh_unitigs_begin_linked: `comp` takes one dense id per unitig, `rows` 4 words
+        /// (KH_COMP_*) per component, either may be null with a cap of 0; `out` (required) takes the 4 words KH_CC_*
+        pub fn kh_unitigs_components_device(ctx: *mut KhCtx, d_comp: *mut u32, comp_cap: u64, d_rows: *mut u64, row_cap: u64, out: *mut u64) -> c_int;
+        pub fn kh_unitigs_components(ctx: *mut KhCtx, comp: *mut u32, comp_cap: u64, rows: *mut u64, row_cap: u64, out: *mut u64) -> c_int;
+        /// one round of dropping the components of src's compacted graph with fewer than `min_kmers` k-mers; `out` takes the 9
+        /// words KH_DROP_* of the header names
+        pub fn kh_drop_components_into(dst: *mut KhCtx, src: *mut KhCtx, min_count: u64, min_kmers: u64, out: *mut u64) -> c_int;
         /// the result as text, formatted on the device; format: 1 = fasta, 2 = tsv, 3 = json (the whole document)
         pub fn kh_result_sorted(ctx: *mut KhCtx, keys: *mut u64, counts: *mut u64, cap: u64,
                                 min_count: u64, n: *mut u64) -> c_int;
@@ -314,6 +321,34 @@ pub const POP_KEPT_KMERS: usize = 5;
 pub const POP_KEPT_COUNT: usize = 6;
 pub const POP_LINKS: usize = 7;
 pub const POP_BUBBLES: usize = 8;
+
+/// `KH_COMP_WORDS`: the words of a component row of [`HipKmerMap::unitigs_components`] -- `COMP_FIRST` (its smallest unitig index),
+/// `COMP_UNITIGS`, `COMP_KMERS`, `COMP_COUNT_SUM`; `KH_CC_WORDS`: the words of the call -- `CC_COMPONENTS`, `CC_SINGLETONS`,
+/// `CC_LARGEST_KMERS`, `CC_ROUNDS` (the hooking rounds of the build).
+pub const COMP_WORDS: usize = 4;
+pub const COMP_FIRST: usize = 0;
+pub const COMP_UNITIGS: usize = 1;
+pub const COMP_KMERS: usize = 2;
+pub const COMP_COUNT_SUM: usize = 3;
+pub const CC_WORDS: usize = 4;
+pub const CC_COMPONENTS: usize = 0;
+pub const CC_SINGLETONS: usize = 1;
+pub const CC_LARGEST_KMERS: usize = 2;
+pub const CC_ROUNDS: usize = 3;
+
+/// `KH_DROP_WORDS`: the words of [`HipKmerMap::drop_components_into`] -- unitigs, components, dropped, dropped_kmers, dropped_count,
+/// kept_kmers, kept_count, links, dropped_unitigs (`DROP_UNITIGS` .. `DROP_DROPPED_UNITIGS`); words 0, 5, 6 and 7 mean what the
+/// `CLIP_*` words mean.
+pub const DROP_WORDS: usize = 9;
+pub const DROP_UNITIGS: usize = 0;
+pub const DROP_COMPONENTS: usize = 1;
+pub const DROP_DROPPED: usize = 2;
+pub const DROP_DROPPED_KMERS: usize = 3;
+pub const DROP_DROPPED_COUNT: usize = 4;
+pub const DROP_KEPT_KMERS: usize = 5;
+pub const DROP_KEPT_COUNT: usize = 6;
+pub const DROP_LINKS: usize = 7;
+pub const DROP_DROPPED_UNITIGS: usize = 8;
 
 /// KH_SET_*: the set operation of `kh_combine_into`.
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
@@ -644,6 +679,17 @@ impl HipKmerMap {
         Ok(out)
     }
 
+    /// One round of dropping small components (`kh_drop_components_into`): the unitigs and links of `src` at `min_count` are built
+    /// on the device and labelled by connected component; the k-mers of every component that holds at least `min_kmers` k-mers are
+    /// added to this table with their counts (`count[key] += c`), the smaller ones -- the isolated debris clipping and popping cannot
+    /// touch -- are left out.  0 or 1 drops nothing; a circular unitig is treated like any other.  `src` is only read; unitigs it had
+    /// begun are released.  Returns the nine words ([`DROP_UNITIGS`] .. [`DROP_DROPPED_UNITIGS`]).
+    pub fn drop_components_into(&mut self, src: &HipKmerMap, min_count: u64, min_kmers: u64) -> Result<[u64; DROP_WORDS], HipError> {
+        let mut out = [0u64; DROP_WORDS];
+        check(self.ctx, unsafe { sys::kh_drop_components_into(self.ctx, src.ctx, min_count, min_kmers, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
     /// [`unitigs`](Self::unitigs) and the links between the unitigs' ends (`kh_unitigs_begin_linked` / `kh_unitigs_copy` /
     /// `kh_unitigs_links_copy` / `kh_unitigs_end`): one word per link -- [`uni_link_from`], [`uni_link_from_sign`], [`uni_link_to`],
     /// [`uni_link_to_sign`] take it apart --, in ascending word order; a link spans k - 1 bases of overlap.  Loops, hairpins and
@@ -805,6 +851,28 @@ impl HipKmerMap {
         err?;
         check(self.ctx, end)?;
         Ok((links, support, stats))
+    }
+
+    /// The connected components of the unitig graph of the table at `min_count` (`kh_unitigs_begin_linked` /
+    /// `kh_unitigs_components` twice / `kh_unitigs_end`).  Returns `(comp, rows, stats)`: the dense component id of every unitig
+    /// (ids ascend with the component's smallest unitig index), `COMP_WORDS` words per component, and the `CC_WORDS` words of the call.
+    pub fn unitigs_components(&self, min_count: u64) -> Result<(Vec<u32>, Vec<u64>, [u64; CC_WORDS]), HipError> {
+        let (mut nu, mut nb, mut nl) = (0u64, 0u64, 0u64);
+        check(self.ctx, unsafe { sys::kh_unitigs_begin_linked(self.ctx, min_count, &mut nu, &mut nb, &mut nl) })?;
+        let mut stats = [0u64; CC_WORDS];
+        let mut rc = unsafe { sys::kh_unitigs_components(self.ctx, std::ptr::null_mut(), 0, std::ptr::null_mut(), 0, stats.as_mut_ptr()) };
+        let mut comp = vec![0u32; nu as usize];
+        let mut rows = vec![0u64; stats[CC_COMPONENTS] as usize * COMP_WORDS];
+        if rc == 0 && nu > 0 {
+            rc = unsafe {
+                sys::kh_unitigs_components(self.ctx, comp.as_mut_ptr(), nu, rows.as_mut_ptr(), stats[CC_COMPONENTS], stats.as_mut_ptr())
+            };
+        }
+        let err = check(self.ctx, rc);  // (before kh_unitigs_end replaces the error text)
+        let end = unsafe { sys::kh_unitigs_end(self.ctx) };
+        err?;
+        check(self.ctx, end)?;
+        Ok((comp, rows, stats))
     }
 
     /// Packed canonical key -> count: the shape of `count_kmers_from_sequences`

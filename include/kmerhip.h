@@ -69,11 +69,11 @@ typedef enum kh_status {
 /* Allocation failures: what KH_ERR_OOM leaves behind.  One rule per kind of call; the comments further down only add to it.
  *   - A READING call takes the table as it is and allocates only for itself: kh_result_size / _copy / _copy_device / _sorted*,
  *     kh_result_text_*, kh_histogram, kh_lookup, kh_profile*, kh_profile_records*, kh_compare, kh_graph_*, kh_unitigs_*,
- *     kh_unitigs_text_begin / kh_unitigs_text_next / kh_unitigs_text_next_device, kh_unitigs_paths / kh_unitigs_paths_device, kh_unitigs_link_support / kh_unitigs_link_support_device and the src side of kh_clip_tips_into / kh_pop_bubbles_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
+ *     kh_unitigs_text_begin / kh_unitigs_text_next / kh_unitigs_text_next_device, kh_unitigs_paths / kh_unitigs_paths_device, kh_unitigs_link_support / kh_unitigs_link_support_device, kh_unitigs_components / kh_unitigs_components_device and the src side of kh_clip_tips_into / kh_pop_bubbles_into / kh_drop_components_into.  When one of its allocations fails it returns KH_ERR_OOM, kh_last_error() names the
  *     allocation, the table is unchanged and the context is NOT poisoned: the same call can be made again.  What the call
  *     allocated is released, except the scratch the context keeps for the next such call where that had been allocated
  *     before the failure: the pinned staging chunks and the copy stream of the host forms, the scan scratch (not after the
- *     sorted results, kh_unitigs_begin*, kh_clip_tips_into and kh_pop_bubbles_into: there nothing stays), the tile arrays of a text stream (a failure of kh_unitigs_text_begin / kh_unitigs_text_next /
+ *     sorted results, kh_unitigs_begin*, kh_unitigs_components*, kh_clip_tips_into, kh_pop_bubbles_into and kh_drop_components_into: there nothing stays), the tile arrays of a text stream (a failure of kh_unitigs_text_begin / kh_unitigs_text_next /
  *     kh_unitigs_text_next_device ends that stream and releases its offsets and chunks; the unitigs stay live), the
  *     chunk and row buffers of kh_profile / kh_profile_records, the words of kh_compare and kh_graph_stats.  kh_destroy
  *     releases them.  (Pushes that were still pending when the reading call came are counted first, as a writing call.)
@@ -666,6 +666,43 @@ int kh_unitigs_link_support_device(kh_ctx *ctx, const uint64_t *d_run_start, uin
 int kh_unitigs_link_support(kh_ctx *ctx, const uint64_t *run_start, uint64_t nrec, const uint32_t *runs, uint64_t n_runs,
                             uint64_t *support, uint64_t cap, uint64_t *out);
 
+/* ---- CONNECTED COMPONENTS: which unitigs hang together (Bandage's component view, per-component length and coverage) ---------- */
+/* The calls work on the live unitigs of kh_unitigs_begin_linked.  Two unitigs are in the same component iff a chain of link words
+ * joins them, ignoring signs and direction: every link has its mirror in the list, so the link array is an undirected edge list.
+ * A link from a unitig to itself (the closing link of a circle, the turns of a loop, a hairpin) joins nothing; a unitig without a
+ * link to another unitig is a component of its own.
+ * OUTPUT: comp[u] (uint32) is the dense id of unitig u's component: ids run 0 .. C-1 in ascending order of the component's
+ *   smallest unitig index, so comp[0] == 0.  rows has C rows of KH_COMP_WORDS words, one per component, in id order.  Unitig order
+ *   does not depend on the table, so the same index content gives the same bytes for every geometry and both table forms.
+ *   Device memory in the device form, host memory in the host form.  out (host memory in both forms, REQUIRED) gets the
+ *   KH_CC_WORDS words; it is complete on KH_OK and on KH_ERR_RANGE, which is how a caller sizes rows.
+ * CAPS: either array may be NULL with a cap of 0: not wanted.  A non-zero comp_cap < n_unitigs or a non-zero row_cap < C is
+ *   KH_ERR_RANGE with nothing written to either array; otherwise nothing at or behind comp[n_unitigs] / rows[C] is written.
+ * ENTRY: both enter as readers, like kh_unitigs_link_support*: kh_stats, the table, the place map and a running
+ *   kh_result_text_* or kh_unitigs_text_* stream are left alone.  KH_ERR_STATE without live unitigs, and after a plain
+ *   kh_unitigs_begin, which built no links (the message names kh_unitigs_begin_linked).  No unitigs: KH_OK, out all zero.
+ * KH_ERR_BAD_ARG (the context stays usable): NULL out; a NULL array with a non-zero cap; comp not 4-byte aligned; rows or out not
+ *   8-byte aligned.
+ * THE LABELS are built by the first call after a kh_unitigs_begin_linked (hook and compress rounds over the link array, then the
+ *   sums per component) and kept with the unitigs: 4 bytes per unitig and 32 per component of device memory of the context's own,
+ *   until kh_unitigs_end, the next begin, kh_reset or kh_destroy; a begin that never asks allocates nothing for them.  Later calls
+ *   of kh_unitigs_components_device allocate nothing and run no kernel, only copies.  KH_ERR_OOM follows the rule of the reading
+ *   calls: the context is not poisoned, the unitigs stay live, nothing of half-built labels stays allocated, and the next call
+ *   tries again. */
+#define KH_COMP_WORDS 4        /* uint64 words per component row */
+#define KH_COMP_FIRST 0        /* its smallest unitig index; rows ascend in it */
+#define KH_COMP_UNITIGS 1
+#define KH_COMP_KMERS 2        /* sum of KH_UNI_KMERS of its unitigs */
+#define KH_COMP_COUNT_SUM 3    /* sum of KH_UNI_COUNT_SUM, modulo 2^64 */
+#define KH_CC_WORDS 4          /* the call's statistics, host memory */
+#define KH_CC_COMPONENTS 0
+#define KH_CC_SINGLETONS 1     /* components of exactly one unitig */
+#define KH_CC_LARGEST_KMERS 2  /* the greatest KH_COMP_KMERS; 0 when there is no unitig */
+#define KH_CC_ROUNDS 3         /* hooking rounds the build ran, the last (empty) one included; the same value on every later call */
+int kh_unitigs_components_device(kh_ctx *ctx, uint32_t *d_comp, uint64_t comp_cap, uint64_t *d_rows, uint64_t row_cap,
+                                 uint64_t *out /* KH_CC_WORDS, host */);
+int kh_unitigs_components(kh_ctx *ctx, uint32_t *comp, uint64_t comp_cap, uint64_t *rows, uint64_t row_cap, uint64_t *out);
+
 /* ---- tip clipping: one round of removing short dead-end branches (what assemblers do first with the compacted graph) --- */
 /* Take the unitigs and links of kh_unitigs_begin_linked(src, min_count): rows, end states (i, +) and (i, -) and link words exactly
  * as defined above.  out(i, s) is the set of links whose from-state is (i, s).
@@ -749,6 +786,35 @@ int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max
 #define KH_POP_LINKS 7            /* links of src's compacted graph */
 #define KH_POP_BUBBLES 8          /* classes of at least two parallel candidates = survivors that beat someone */
 int kh_pop_bubbles_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out /* KH_POP_WORDS, host */);
+
+/* ---- dropping small components: removing the isolated debris that clipping and popping cannot touch (the third cleaning step) --- */
+/* Take the unitigs and links of kh_unitigs_begin_linked(src, min_count) and their connected components as
+ * kh_unitigs_components defines them.
+ * DROPPED: a component is dropped iff the k-mers of all its unitigs together (its KH_COMP_KMERS) number fewer than min_kmers.
+ *   min_kmers of 0 or 1 drops nothing.  A circular unitig is treated like any other: whether a short plasmid is debris is the
+ *   caller's choice of bound.  One call is one round, and it is idempotent: what survives has min_kmers k-mers or more in each
+ *   component, and removing whole components changes no other.
+ * RESULT: every k-mer of every unitig of a surviving component is added to dst with its count from src -- count += c, exactly as
+ *   kh_merge_pairs_device does.  K-mers of src below min_count are not in S and are not copied.
+ * ENTRY and ERRORS are those of kh_clip_tips_into, word for word: src is entered as kh_unitigs_begin_linked enters it (pending
+ *   pushes are counted first, the table is read in the form it is in, a text stream in progress ends, the partition buffers serve
+ *   as scratch, a shard is KH_ERR_STATE, more than 2^31 - 1 nodes is KH_ERR_RANGE); its table, counts and kh_stats are unchanged.
+ *   Any unitigs src had begun are RELEASED.  dst is entered as kh_combine_into enters its target.  dst == src, a NULL src or a
+ *   NULL out is KH_ERR_BAD_ARG; different k or different devices are KH_ERR_BAD_ARG, different shard states KH_ERR_STATE; every
+ *   such refusal leaves both contexts usable.  No memory for the call's scratch is KH_ERR_OOM with src usable and dst holding
+ *   what it held.  An empty S is KH_OK with all words 0.  The error text is on dst.
+ * Words 0, 5, 6 and 7 mean what the KH_CLIP_* words of the same index mean. */
+#define KH_DROP_WORDS 9
+#define KH_DROP_UNITIGS 0          /* unitigs of src at min_count */
+#define KH_DROP_COMPONENTS 1
+#define KH_DROP_DROPPED 2          /* components dropped */
+#define KH_DROP_DROPPED_KMERS 3
+#define KH_DROP_DROPPED_COUNT 4    /* modulo 2^64 */
+#define KH_DROP_KEPT_KMERS 5       /* pairs added to dst */
+#define KH_DROP_KEPT_COUNT 6       /* sum of their counts, modulo 2^64 */
+#define KH_DROP_LINKS 7            /* links of src's compacted graph */
+#define KH_DROP_DROPPED_UNITIGS 8
+int kh_drop_components_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t min_kmers, uint64_t *out /* KH_DROP_WORDS, host */);
 
 /* ---- multi-GPU merge (no reference counterpart) ----------- */
 /* Owner shard of a packed canonical k-mer among nparts shards: a fast-range of the top bits of

@@ -14,6 +14,8 @@
 //   locate.hip    kh_unitigs_locate*: where on those unitigs the k-mer of every window start of new sequences lies (the place map)
 //   paths.hip     kh_unitigs_paths*: those places folded per record into runs along one unitig, and the coverage per unitig
 //   support.hip   kh_unitigs_link_support*: how many of those records walk every link between the unitigs (the link index)
+//   components.hip  kh_unitigs_components*: which unitigs hang together (hook and compress over the link array, sums per component); its
+//                 labelling and decide launches also serve kh_drop_components_into, the third rule of unitig.hip's clip_step()
 //   sort.hip      kh_result_sorted*: the result pairs in ascending key order (a device radix sort; format.hip streams it as text)
 //   exchange.hip  kh_comm_* / kh_merge_across / kh_group_*: the exchange between contexts (RCCL over xGMI, or the local hub)
 //   level1_*.hip  the level-1 kernels, one instance per k
@@ -417,6 +419,15 @@ struct kh_ctx {
         // for a state without links -- and behind them the KH_SUP_WORDS words the kernel adds up.  Built by the first support call after a
         // kh_unitigs_begin_linked ((2 * n_unitigs + KH_SUP_WORDS) * 8 bytes), released by unitigs_release().
         u64 *link_first = nullptr;
+        // kh_unitigs_components* (components.hip): the labels.  One allocation, built by the first components call after a
+        // kh_unitigs_begin_linked and released by unitigs_release(): n_comp rows of KH_COMP_WORDS words, then one uint32 per unitig
+        // (32 bytes per component, 4 per unitig); the KH_CC_WORDS words of the build stay here in host memory.  comp_built also
+        // stands for "no unitigs": then nothing is allocated.
+        bool comp_built = false;
+        u64 *comp_rows = nullptr;      // (the allocation)
+        uint32_t *comp = nullptr;      // (behind the rows)
+        u64 n_comp = 0;
+        u64 cc[KH_CC_WORDS] = {0, 0, 0, 0};
         // kh_unitigs_text_* (unitig_text.hip): these unitigs as text.  begin sizes every record and link line and scans both; next formats
         // ranges of whole tiles of UT_TILE bytes into one of two device chunks of the stream's OWN -- never the partition buffers: a
         // kh_result_text_* stream may run beside it -- and hands their bytes out: chunk i + 1 is formatted on `stream` while chunk i
@@ -498,13 +509,13 @@ struct Entry {
 // Slot indices are stable for as long as un.live holds: only `reader` entries keep it, and both reader presets below set narrow_ok,
 // so that enter() neither widens the image nor moves, grows or clears a table that holds counts (nothing is pending behind live
 // unitigs: a push is no reader).  The place map of kh_unitigs_locate* (Unitigs::where) is indexed by slot and relies on it.
-// The pair and dense merges, the exports by owner, kh_comm_init, the dst of kh_combine_into / kh_clip_tips_into / kh_pop_bubbles_into: a cleared
+// The pair and dense merges, the exports by owner, kh_comm_init, the dst of kh_combine_into / kh_clip_tips_into / kh_pop_bubbles_into / kh_drop_components_into: a cleared
 // 16-byte table, everything pending counted, whatever hangs on the table's content (text stream, unitigs, merge window) ended.
 constexpr Entry ENTER_WRITE{};
 // kh_finish, kh_result_size, kh_histogram, kh_lookup, kh_profile*, the sources of kh_compare / kh_combine_into, kh_graph_*,
 // the copies of the unitigs, kh_result_text_begin: everything pending counted, the table in the form it is in, nothing ended.
 constexpr Entry ENTER_READ{true, true, false, true, true};
-// kh_result_copy*, kh_result_sorted*, kh_region_unit_counts_device, kh_unitigs_begin*, the src of kh_clip_tips_into / kh_pop_bubbles_into,
+// kh_result_copy*, kh_result_sorted*, kh_region_unit_counts_device, kh_unitigs_begin*, the src of kh_clip_tips_into / kh_pop_bubbles_into / kh_drop_components_into,
 // kh_merge_across: reads the table in the form it is in, but may take the idle partition buffers -- a text stream, whose chunks
 // live there, ends (and with it the unitigs).
 constexpr Entry ENTER_READ_TAKE{true, true, false, true, false};
@@ -604,6 +615,16 @@ int join_check(kh_ctx *err, const char *who, const kh_ctx *a, const kh_ctx *b, c
 // ---- unitig.hip
 void unitigs_release(kh_ctx *c);  // kh_unitigs_end / kh_reset / kh_destroy: the rows, bases and links of the last kh_unitigs_begin[_linked]
 inline unsigned uni_grid(u64 items) { return (unsigned)grid_for(items); }  // every launch of unitig.hip and unitig_text.hip: KMERHIP_GRID_CAP applies
+// ---- components.hip
+// What kh_unitigs_components* and the drop rule of clip_step() share.  The unitigs and links are c->un's; everything is queued on
+// c->stream.  parent: n_unitigs words, sums: KH_CSUM_WORDS words per unitig (only a root's are meaningful), d_flag: one word --
+// all scratch of the caller.  components_label leaves parent[u] = the smallest unitig index of u's component and the sums of every
+// root, and drains the stream once per hooking round; *rounds = the rounds it ran.  components_drop_launch queues the decide kernel
+// of kh_drop_components_into: removed[u] and seven of the KH_DROP_WORDS words (added to `words`, which the caller has zeroed).
+constexpr u64 KH_CSUM_WORDS = 3;  // UNITIGS, KMERS, COUNT_SUM of the root's component
+// before_sums (optional): called between the last round and the sums' launch (the trace's event).
+int components_label(kh_ctx *c, uint32_t *parent, u64 *sums, uint32_t *d_flag, u64 *rounds, const std::function<void()> &before_sums = nullptr);
+int components_drop_launch(kh_ctx *c, const uint32_t *parent, const u64 *sums, const u64 *loff, u64 min_kmers, uint8_t *removed, u64 *words);
 // ---- unitig_text.hip
 void unitigs_text_release(kh_ctx *c);  // the offsets, chunks and events of a kh_unitigs_text_* stream (unitigs_release calls it)
 // ---- profile.hip

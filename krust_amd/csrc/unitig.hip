@@ -36,6 +36,9 @@
 //   pop_exits_kernel           per unitig: its row, the offsets of its two end states and its two links -> one exit word
 //   pop_decide_kernel          per candidate: the links out of its + exit reversed (the unitigs that enter the same place), their exit
 //                              words, the rows of the parallel ones (kh_pop_beats) -> one popped byte; seven of the nine words
+// kh_drop_components_into only, in the same place (one round of dropping small components, include/kmerhip.h); the keep kernel is clip's:
+//   components_label           components.hip: hook and compress rounds over the links, then the sums per root
+//   comp_drop_kernel           components.hip: per unitig, its component's k-mers against the bound -> one dropped byte; seven of the nine words
 // No kernel waits for another workgroup, and no device loop is without a bound.  Rates were not measured (profiles/README.md r13).
 #include "ctx.hip.h"
 #include "probe.hip.h"
@@ -567,6 +570,9 @@ KH_GLOBAL __launch_bounds__(BLOCK) void clip_keep_kernel(TableGeom tg, u64 q0, u
 // ---- bubble popping (kh_pop_bubbles_into) -------------------------------------------------------------------------------------
 static_assert(KH_POP_KEPT_KMERS == KH_CLIP_KEPT_KMERS && KH_POP_KEPT_COUNT == KH_CLIP_KEPT_COUNT && KH_POP_WORDS >= KH_CLIP_WORDS,
               "clip_keep_kernel writes the kept words of both rules");
+static_assert(KH_DROP_KEPT_KMERS == KH_CLIP_KEPT_KMERS && KH_DROP_KEPT_COUNT == KH_CLIP_KEPT_COUNT && KH_DROP_UNITIGS == KH_CLIP_UNITIGS &&
+                  KH_DROP_LINKS == KH_CLIP_LINKS && KH_DROP_WORDS <= KH_POP_WORDS,
+              "clip_keep_kernel writes the kept words of the drop rule too, clip_step() checks its unitigs and links, ClipJob holds its words");
 #define KH_POP_NO_EXITS (~0ull)  // no candidate (a to-state is below 2^32 - 2: no pair of them gives this word)
 
 // Per unitig: the unordered pair of the states its two ends enter, min << 32 | max, where it is a candidate (the rule:
@@ -684,6 +690,7 @@ void unitigs_release(kh_ctx *c) {
     if (c->un.links) (void)dev_free(c->un.links);
     if (c->un.where) (void)dev_free(c->un.where);  // (the place map of kh_unitigs_locate*, locate.hip)
     if (c->un.link_first) (void)dev_free(c->un.link_first);  // (the link index of kh_unitigs_link_support*, support.hip)
+    if (c->un.comp_rows) (void)dev_free(c->un.comp_rows);  // (the labels of kh_unitigs_components*, components.hip: rows and ids in one)
     c->un = kh_ctx::Unitigs();
 }
 
@@ -713,32 +720,43 @@ int unitig_rank(kh_ctx *c, const uint32_t *next, u64 states, kh::UniRank *cur, k
     return KH_OK;
 }
 
-// The two rules that remove unitigs behind the links: which pair of decision kernels runs in front of the keep loop.
-enum ClipMode { CLIP_TIPS, CLIP_BUBBLES };
+// The three rules that remove unitigs behind the links: which decision kernels run in front of the keep loop.
+enum ClipMode { CLIP_TIPS, CLIP_BUBBLES, CLIP_COMPONENTS };
+inline u64 clip_words(ClipMode m) { return m == CLIP_TIPS ? KH_CLIP_WORDS : m == CLIP_BUBBLES ? KH_POP_WORDS : KH_DROP_WORDS; }
 
-// kh_clip_tips_into / kh_pop_bubbles_into: the rule, the target and the rule's bound in, the eight / nine words out.
+// kh_clip_tips_into / kh_pop_bubbles_into / kh_drop_components_into: the rule, the target and the rule's bound in, the eight / nine words out.
 struct ClipJob {
     ClipMode mode;
     kh_ctx *dst;
-    u64 max_kmers;
+    u64 max_kmers;            // (kh_drop_components_into: its min_kmers)
     u64 words[KH_POP_WORDS];  // (KH_CLIP_WORDS of them for the tips)
     bool on_dst;              // a failure came from dst's side: its text is there already
 };
 
-// One round of tip clipping or bubble popping behind the links of c, while unitigs_build's scratch is live: the rule's two decision
-// kernels on c's stream -- they leave one "removed" byte per unitig --, then the surviving nodes into job->dst on ITS stream, in
+// One round of tip clipping, bubble popping or component dropping behind the links of c, while unitigs_build's scratch is live: the
+// rule's decision kernels on c's stream -- they leave one "removed" byte per unitig --, then the surviving nodes into job->dst on ITS stream, in
 // ranges it has room for (as combine_scan of join.hip).  Every failure before the first insert leaves dst as it was.
 int clip_step(kh_ctx *c, ClipJob *job, CallScratch &sc, u64 n, u64 nu, u64 nl, const u64 *keys, const u64 *counts, const uint32_t *order,
               const uint32_t *ordu, const u64 *loff, uint32_t *d_err) {
     kh_ctx *const dst = job->dst;
-    const bool pop = job->mode == CLIP_BUBBLES;
-    const u64 nwords = pop ? KH_POP_WORDS : KH_CLIP_WORDS;
-    void *const cand = sc.take(pop ? nu * sizeof(u64) : nu);  // the tips' candidate bytes / the bubbles' exit words
+    const bool pop = job->mode == CLIP_BUBBLES, drop = job->mode == CLIP_COMPONENTS;
+    const u64 nwords = clip_words(job->mode);
+    // the tips' candidate bytes / the bubbles' exit words / the components' labels
+    void *const cand = sc.take(drop ? nu * sizeof(uint32_t) : pop ? nu * sizeof(u64) : nu);
+    u64 *const sums = drop ? (u64 *)sc.take(nu * KH_CSUM_WORDS * sizeof(u64)) : nullptr;  // (per root: components.hip)
     uint8_t *const clipped = (uint8_t *)sc.take(nu);
     u64 *const words = (u64 *)sc.take(nwords * sizeof(u64));
-    if (!cand || !clipped || !words) return soft_oom(c, pop ? "device memory for the bubble popping's scratch" : "device memory for the tip clipping's scratch");
+    if (!cand || !clipped || !words || (drop && !sums))
+        return soft_oom(c, drop  ? "device memory for the component dropping's scratch"
+                           : pop ? "device memory for the bubble popping's scratch"
+                                 : "device memory for the tip clipping's scratch");
     HIP_TRY(c, hipMemsetAsync(words, 0, nwords * sizeof(u64), c->stream));
-    if (pop) {
+    if (drop) {
+        u64 rounds = 0;
+        int rc = components_label(c, (uint32_t *)cand, sums, d_err - 1, &rounds);  // (d_err - 1: unitigs_build's "something changed" word, idle by now)
+        if (rc == KH_OK) rc = components_drop_launch(c, (const uint32_t *)cand, sums, loff, job->max_kmers, clipped, words);
+        if (rc != KH_OK) return rc;
+    } else if (pop) {
         hipLaunchKernelGGL(kh::pop_exits_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, job->max_kmers, (const u64 *)c->un.rows, loff,
                            (const u64 *)c->un.links, (u64 *)cand, d_err);
         hipLaunchKernelGGL(kh::pop_decide_kernel, dim3(uni_grid(nu)), dim3(kh::BLOCK), 0, c->stream, nu, nl, (const u64 *)c->un.rows, loff,
@@ -755,8 +773,9 @@ int clip_step(kh_ctx *c, ClipJob *job, CallScratch &sc, u64 n, u64 nu, u64 nl, c
     HIP_TRY(c, hipMemcpyAsync(job->words, words, nwords * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the clipped bytes are complete: dst's stream may read them)
     if (bad || job->words[KH_CLIP_UNITIGS] != nu || job->words[KH_CLIP_LINKS] != nl)
-        return fail(c, KH_ERR_STATE, pop ? "kh_pop_bubbles_into: a candidate is not among the unitigs that enter its own exit, or the links do not add up (internal error)"
-                                         : "kh_clip_tips_into: a candidate is not among its own rivals, or the links do not add up (internal error)");
+        return fail(c, KH_ERR_STATE, drop  ? "kh_drop_components_into: the unitigs or the links do not add up (internal error)"
+                                     : pop ? "kh_pop_bubbles_into: a candidate is not among the unitigs that enter its own exit, or the links do not add up (internal error)"
+                                           : "kh_clip_tips_into: a candidate is not among its own rivals, or the links do not add up (internal error)");
     int rc = KH_OK;
     job->on_dst = true;
     const u64 step = SUB_TILES * kh::TILE;
@@ -773,14 +792,14 @@ int clip_step(kh_ctx *c, ClipJob *job, CallScratch &sc, u64 n, u64 nu, u64 nl, c
         q0 += m;
     }
     if (rc == KH_OK && hipMemcpyAsync(job->words + KH_CLIP_KEPT_KMERS, words + KH_CLIP_KEPT_KMERS, 2 * sizeof(u64), hipMemcpyDeviceToHost, dst->stream) != hipSuccess)
-        rc = fail(dst, KH_ERR_HIP, pop ? "kh_pop_bubbles_into: the kept words" : "kh_clip_tips_into: the kept words");
+        rc = fail(dst, KH_ERR_HIP, drop ? "kh_drop_components_into: the kept words" : pop ? "kh_pop_bubbles_into: the kept words" : "kh_clip_tips_into: the kept words");
     if (rc == KH_OK) rc = sync_counters(dst);  // (complete when it returns; an upsert without a free slot shows here)
     else (void)hipStreamSynchronize(dst->stream);  // (before the scratch goes back)
     return rc;
 }
 
 // linked: kh_unitigs_begin_linked -- the link array behind the same kernels; nothing of it is launched or allocated without.
-// clip: kh_clip_tips_into / kh_pop_bubbles_into -- linked, without the base array, and clip_step() behind the links.
+// clip: kh_clip_tips_into / kh_pop_bubbles_into / kh_drop_components_into -- linked, without the base array, and clip_step() behind the links.
 int unitigs_build(kh_ctx *c, u64 n, u64 mc, CallScratch &sc, bool linked, ClipJob *clip = nullptr) {
     const uint32_t n32 = (uint32_t)n, k = c->k;
     const u64 states = 2 * n;
@@ -982,7 +1001,7 @@ extern "C" int kh_unitigs_begin_linked(kh_ctx *c, uint64_t min_count, uint64_t *
 namespace khi {
 namespace {
 
-// kh_clip_tips_into and kh_pop_bubbles_into: src's unitigs and links are built as kh_unitigs_begin_linked builds them (without the
+// kh_clip_tips_into, kh_pop_bubbles_into and kh_drop_components_into: src's unitigs and links are built as kh_unitigs_begin_linked builds them (without the
 // bases), decided by the rule of `mode` and handed on while the scratch is live, and released again: nothing of them outlives the call.
 int clip_into(const char *who, ClipMode mode, kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out) {
     if (!dst) return KH_ERR_BAD_ARG;
@@ -1016,7 +1035,7 @@ int clip_into(const char *who, ClipMode mode, kh_ctx *dst, kh_ctx *src, uint64_t
         unitigs_release(src);
         if (rc != KH_OK) return job.on_dst ? rc : from_src(rc);
     }
-    memcpy(out, job.words, (mode == CLIP_BUBBLES ? KH_POP_WORDS : KH_CLIP_WORDS) * sizeof(u64));
+    memcpy(out, job.words, clip_words(mode) * sizeof(u64));
     return KH_OK;
 }
 
@@ -1029,6 +1048,10 @@ extern "C" int kh_clip_tips_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, u
 
 extern "C" int kh_pop_bubbles_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t max_kmers, uint64_t *out) {
     return clip_into("kh_pop_bubbles_into", CLIP_BUBBLES, dst, src, min_count, max_kmers, out);
+}
+
+extern "C" int kh_drop_components_into(kh_ctx *dst, kh_ctx *src, uint64_t min_count, uint64_t min_kmers, uint64_t *out) {
+    return clip_into("kh_drop_components_into", CLIP_COMPONENTS, dst, src, min_count, min_kmers, out);
 }
 
 extern "C" int kh_unitigs_links_copy_device(kh_ctx *c, uint64_t *d_links, uint64_t cap) {

@@ -135,6 +135,18 @@ POP_WORDS = 9
 POP_UNITIGS, POP_CANDIDATES, POP_POPPED, POP_POPPED_KMERS, POP_POPPED_COUNT, POP_KEPT_KMERS, POP_KEPT_COUNT, POP_LINKS, POP_BUBBLES = range(9)
 POP_NAMES = ("unitigs", "candidates", "popped", "popped_kmers", "popped_count", "kept_kmers", "kept_count", "links", "bubbles")
 
+# KH_COMP_*: the words of a component row of kh_unitigs_components* -- its smallest unitig index, its unitigs, the sums of their KMERS
+# and COUNT_SUM; KH_CC_*: the words of the call -- components, those of one unitig, the greatest KMERS of a row, the hooking rounds
+COMP_WORDS, COMP_FIRST, COMP_UNITIGS, COMP_KMERS, COMP_COUNT_SUM = 4, 0, 1, 2, 3
+CC_WORDS, CC_COMPONENTS, CC_SINGLETONS, CC_LARGEST_KMERS, CC_ROUNDS = 4, 0, 1, 2, 3
+CC_NAMES = ("components", "singletons", "largest_kmers", "rounds")
+
+# KH_DROP_*: the words of kh_drop_components_into
+DROP_WORDS = 9
+(DROP_UNITIGS, DROP_COMPONENTS, DROP_DROPPED, DROP_DROPPED_KMERS, DROP_DROPPED_COUNT, DROP_KEPT_KMERS, DROP_KEPT_COUNT, DROP_LINKS,
+ DROP_DROPPED_UNITIGS) = range(9)
+DROP_NAMES = ("unitigs", "components", "dropped", "dropped_kmers", "dropped_count", "kept_kmers", "kept_count", "links", "dropped_unitigs")
+
 
 _SET_OPS = {"intersect": SET_INTERSECT, "union": SET_UNION, "subtract": SET_SUBTRACT, "count-subtract": SET_COUNT_SUBTRACT}
 _CALCS = {"min": CALC_MIN, "max": CALC_MAX, "sum": CALC_SUM, "left": CALC_LEFT, "right": CALC_RIGHT}
@@ -220,7 +232,10 @@ SYMBOLS = {
     "kh_unitigs_paths": (C.c_int, [_P, _P, _P, _U64, _P, _U64, _P, _P, _U64, _P, C.POINTER(_U64)]),
     "kh_unitigs_link_support_device": (C.c_int, [_P, _P, _U64, _P, _U64, _P, _U64, _P]),
     "kh_unitigs_link_support": (C.c_int, [_P, _P, _U64, _P, _U64, _P, _U64, _P]),
+    "kh_unitigs_components_device": (C.c_int, [_P, _P, _U64, _P, _U64, _P]),
+    "kh_unitigs_components": (C.c_int, [_P, _P, _U64, _P, _U64, _P]),
     "kh_clip_tips_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
+    "kh_drop_components_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_pop_bubbles_into": (C.c_int, [_P, _P, _U64, _U64, _P]),
     "kh_owner": (C.c_uint32, [_U64, C.c_uint32, C.c_uint32]),
     "kh_set_shard": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -712,6 +727,7 @@ class DeviceCounter:
         nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         self._check(lib().kh_unitigs_begin_linked(self._h, int(min_count), C.byref(nu), C.byref(nb), C.byref(nl)))
         self._n_links = int(nl.value)   # (what unitigs_link_support sizes a fresh array with)
+        self._n_unitigs = int(nu.value)  # (and unitigs_components)
         return int(nu.value), int(nb.value), int(nl.value)
 
     def unitigs_links_copy(self, n_links):
@@ -838,6 +854,49 @@ class DeviceCounter:
         self._check(lib().kh_unitigs_link_support_device(self._h, ptr(d_run_start), int(nrec), ptr(d_runs), int(n_runs), ptr(d_support), int(cap),
                                                          out.ctypes.data))
         return dict(zip(SUP_NAMES, (int(x) for x in out)))
+
+    # -- connected components of the unitig graph -------------------------------
+    def unitigs_components(self, n_unitigs=None):
+        """kh_unitigs_components: which unitigs of unitigs_begin_linked hang together through links (signs and direction ignored,
+        self links join nothing).  Returns (comp, rows, stats): comp a uint32 array with the dense component id of every unitig
+        (ids ascend with the component's smallest unitig index), rows a (components, 4) uint64 array with the columns COMP_FIRST,
+        COMP_UNITIGS, COMP_KMERS and COMP_COUNT_SUM, stats a dict of components, singletons, largest_kmers and rounds.  n_unitigs:
+        None for the count of this object's last unitigs_begin_linked.  The first call after a begin builds the labels on the
+        device; later ones copy."""
+        if n_unitigs is None:
+            if getattr(self, "_n_unitigs", None) is None:
+                raise ValueError("n_unitigs=None needs a unitigs_begin_linked made through this object")
+            n_unitigs = self._n_unitigs
+        out = np.zeros(CC_WORDS, dtype=np.uint64)
+        self._check(lib().kh_unitigs_components(self._h, None, 0, None, 0, out.ctypes.data))  # (sizes the rows)
+        comp = np.zeros(int(n_unitigs), dtype=np.uint32)
+        rows = np.zeros((int(out[CC_COMPONENTS]), COMP_WORDS), dtype=np.uint64)
+        self._check(lib().kh_unitigs_components(self._h, comp.ctypes.data if comp.size else None, comp.size,
+                                                rows.ctypes.data if rows.size else None, rows.shape[0], out.ctypes.data))
+        return comp, rows, dict(zip(CC_NAMES, (int(x) for x in out)))
+
+    def unitigs_components_device(self, d_comp, comp_cap, d_rows, row_cap):
+        """The same into device memory: integer addresses or torch tensors of comp_cap uint32 words and row_cap * 4 uint64 words,
+        either None with a cap of 0 (not wanted).  Returns (status, stats) with status KH_OK or KH_ERR_RANGE -- a cap was too
+        small: stats is complete and nothing was written, size the arrays and call again --, and raises for every other status."""
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        out = np.zeros(CC_WORDS, dtype=np.uint64)
+        rc = lib().kh_unitigs_components_device(self._h, ptr(d_comp), int(comp_cap), ptr(d_rows), int(row_cap), out.ctypes.data)
+        if rc != KH_ERR_RANGE:
+            self._check(rc)
+        return rc, dict(zip(CC_NAMES, (int(x) for x in out)))
+
+    # -- dropping small components: one round over the compacted graph ----------
+    def drop_components_into(self, src, min_count=1, min_kmers=None):
+        """kh_drop_components_into: the k-mers of every unitig of `src`'s compacted graph at min_count whose connected component
+        holds at least min_kmers k-mers (None: 2 * k) are added to THIS table with their counts from src (count[key] += c); smaller
+        components -- the isolated debris clipping and popping cannot touch -- are left out.  0 or 1 drops nothing.  src's table
+        is only read, unitigs it had begun are released; this table must not be src.  Returns the nine words as a dict: unitigs,
+        components, dropped, dropped_kmers, dropped_count, kept_kmers, kept_count, links, dropped_unitigs."""
+        out = np.zeros(DROP_WORDS, dtype=np.uint64)
+        mk = 2 * self.k if min_kmers is None else int(min_kmers)
+        self._check(lib().kh_drop_components_into(self._h, src._h, int(min_count), mk, out.ctypes.data))
+        return dict(zip(DROP_NAMES, (int(x) for x in out)))
 
     # -- tip clipping: one round over the compacted graph ---------------------
     def clip_tips_into(self, src, min_count=1, max_kmers=None):

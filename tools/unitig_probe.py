@@ -52,6 +52,17 @@ With --support, in ONE PROCESS PER SIZE, the read support per link (kh_unitigs_l
   split_ms               the traced split of one support call (the index build, link_support_kernel) and of the paths call before it
                          (path_cover_kernel is the yardstick: one lane per row, atomics per row) -- a second context with KH_FLAG_TRACE
   host_route             what the call replaces: the rows copied back, then np.searchsorted of the crossing words in the link array
+With --components, in ONE PROCESS PER SIZE, the connected components of the unitig graph (kh_unitigs_components*) and the drop rule:
+  unitigs_begin_linked   kh_unitigs_begin_linked(1), as above; components_first = the first kh_unitigs_components_device behind it (it
+                         builds the labels), components_cached = the second (copies only) -- six begins, the first not counted;
+                         first_over_begin = the ratio of the medians
+  stats                  components, singletons, largest_kmers, rounds of the call
+  split_ms               the traced split of one first call -- the rounds (hook, compress and the flag read-back per round), the sums,
+                         ids and rows -- a second context with KH_FLAG_TRACE
+  drop_components_into   kh_drop_components_into(1, min_kmers = 2 k) into a fresh context hinted with the node count; clip_tips_into =
+                         kh_clip_tips_into(1, k) into the same, the two alternating, kh_reset (not timed) before every call
+  host_route             what the call replaces: kh_unitigs_links_copy, then connected components on the host -- scipy.sparse.csgraph
+                         where scipy is importable, else a numpy hook-and-compress; host_route_by names which; its labels must agree
 The measurement runs in a child process with a timeout; a failure is reported as {"error": ...}."""
 import argparse
 import json
@@ -519,7 +530,125 @@ def measure_support_one(n, k):
     return out
 
 
+def measure_components_one(n, k):
+    import re
+    import tempfile
+    import numpy as np
+    import torch
+    from krust_amd import native
+    rl = 150
+    t = torch.empty(n * (rl + 1), dtype=torch.uint8, device="cuda:0")
+    native.synth_reads_device(t.data_ptr(), None, 20260130, 1 << 28, rl, 0, n, device=0)
+    torch.cuda.synchronize()
+
+    def table(trace):
+        a = native.DeviceCounter(k, device=0, trace=trace)
+        a.push_device(t.data_ptr(), None, t.numel())
+        return a, a.finish()
+
+    a, st = table(False)
+    nodes = st["distinct"]
+    out = {"k": k, "reads": n, "table": {f: st[f] for f in ("distinct", "kmers", "table_slots", "slot_bytes")}}
+    nu, nb, nl = a.unitigs_begin_linked(1)
+    rc, stats = a.unitigs_components_device(None, 0, None, 0)
+    nc = stats["components"]
+    d_comp = torch.empty(max(nu, 1), dtype=torch.int32, device="cuda:0")
+    d_rows = torch.empty(max(nc, 1) * native.COMP_WORDS, dtype=torch.int64, device="cuda:0")
+    torch.cuda.synchronize()
+    out.update(unitigs=nu, links=nl, stats=stats)
+    tb, tf, tc = [], [], []
+    for rep in range(6):                          # one warm round, then five
+        t0 = time.perf_counter()
+        a.unitigs_begin_linked(1)
+        t1 = time.perf_counter()
+        a.unitigs_components_device(d_comp, nu, d_rows, nc)
+        t2 = time.perf_counter()
+        a.unitigs_components_device(d_comp, nu, d_rows, nc)
+        t3 = time.perf_counter()
+        tb.append(t1 - t0), tf.append(t2 - t1), tc.append(t3 - t2)
+    med = lambda ts: {"median_s": sorted(ts[1:])[len(ts[1:]) // 2], "spread_s": max(ts[1:]) - min(ts[1:])}
+    out["unitigs_begin_linked"], out["components_first"], out["components_cached"] = med(tb), med(tf), med(tc)
+    out["first_over_begin"] = out["components_first"]["median_s"] / out["unitigs_begin_linked"]["median_s"]
+    comp = d_comp.cpu().numpy().view(np.uint32)[:nu]
+    rows = d_rows.cpu().numpy().view(np.uint64)[:nc * native.COMP_WORDS].reshape(nc, native.COMP_WORDS)
+    assert int(rows[:, native.COMP_UNITIGS].sum()) == nu and int(rows[:, native.COMP_KMERS].sum()) == nodes
+    try:
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        by = "scipy.sparse.csgraph.connected_components"
+    except ImportError:
+        connected_components, by = None, "numpy hook and compress"
+    got = {}
+
+    def host_route():
+        links = a.unitigs_links_copy(nl)
+        fr, to = (links >> np.uint64(33)).astype(np.int64), ((links & np.uint64(0xFFFFFFFF)) >> np.uint64(1)).astype(np.int64)
+        if connected_components is not None:
+            g = coo_matrix((np.ones(fr.size, dtype=np.int8), (fr, to)), shape=(nu, nu))
+            got["n"], got["labels"] = connected_components(g, directed=False)
+            return
+        sel = fr < to
+        x, y = fr[sel], to[sel]
+        parent = np.arange(nu, dtype=np.int64)
+        while True:
+            ra, rb = parent[x], parent[y]
+            d = ra != rb
+            if not d.any():
+                break
+            np.minimum.at(parent, np.maximum(ra, rb)[d], np.minimum(ra, rb)[d])
+            while True:
+                nxt = parent[parent]
+                if np.array_equal(nxt, parent):
+                    break
+                parent = nxt
+        got["labels"], got["n"] = parent, int(np.sum(parent == np.arange(nu)))
+
+    out["host_route"] = dict(timed(host_route), host_route_by=by)
+    first = np.full(got["labels"].max() + 1 if nu else 0, nu, dtype=np.int64)           # the host's labels, made the library's: by first unitig
+    np.minimum.at(first, got["labels"], np.arange(nu))
+    assert got["n"] == nc and np.array_equal(np.searchsorted(np.unique(first[got["labels"]]), first[got["labels"]]), comp)
+    a.unitigs_end()
+    b = native.DeviceCounter(k, device=0, capacity_hint=nodes)
+    words = {}
+    tcl, tdr = [], []
+    for rep in range(6):                          # one warm round, then five, the two calls alternating
+        for name, fn, ts in (("clip", lambda: b.clip_tips_into(a, 1, k), tcl), ("drop", lambda: b.drop_components_into(a, 1, 2 * k), tdr)):
+            b.reset()
+            t0 = time.perf_counter()
+            words[name] = fn()
+            ts.append(time.perf_counter() - t0)
+    out["clip_tips_into"], out["drop_components_into"] = med(tcl), med(tdr)
+    out["drop_words"] = words["drop"]
+    sb = b.finish()
+    assert sb["distinct"] == words["drop"]["kept_kmers"] and words["drop"]["kept_kmers"] + words["drop"]["dropped_kmers"] == nodes
+    assert words["drop"]["components"] == nc and words["drop"]["dropped"] == int(np.sum(rows[:, native.COMP_KMERS] < np.uint64(2 * k)))
+    b.close()
+    a.close()
+    # the split: one traced first call of a second context, the line read back from the process's stderr
+    c, _ = table(True)
+    c.unitigs_begin_linked(1)
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile() as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            c.unitigs_components_device(d_comp, nu, d_rows, nc)
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        text = tmp.read().decode(errors="replace")
+    line = [l for l in text.splitlines() if "kh_unitigs_components_device:" in l]
+    out["split_ms"] = ({name.strip().replace(" ", "_"): float(v) for name, v in re.findall(r"([a-z ]+) ([0-9.]+) ms", line[-1])} if line else {"error": text[-500:]})
+    c.unitigs_end()
+    c.close()
+    return out
+
+
 def measure(args):
+    if args.components:
+        print("RESULT " + json.dumps([measure_components_one(n, args.k) for n in args.reads]))
+        return
     if args.support:
         print("RESULT " + json.dumps([measure_support_one(n, args.k) for n in args.reads]))
         return
@@ -547,13 +676,14 @@ def main():
     ap.add_argument("--locate", action="store_true", help="kh_unitigs_locate* beside kh_profile* and kh_unitigs_begin, one process per size")
     ap.add_argument("--paths", action="store_true", help="kh_unitigs_paths* beside kh_unitigs_locate* on the reads of --locate, one process per size")
     ap.add_argument("--support", action="store_true", help="kh_unitigs_link_support_device behind kh_unitigs_paths_device on the reads of --paths, one process per size")
+    ap.add_argument("--components", action="store_true", help="kh_unitigs_components_device behind kh_unitigs_begin_linked, kh_drop_components_into beside kh_clip_tips_into, one process per size")
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
         measure(args)
         return
-    if args.text or args.locate or args.paths or args.support:   # one process per size
-        which = "--support" if args.support else "--paths" if args.paths else "--locate" if args.locate else "--text"
+    if args.text or args.locate or args.paths or args.support or args.components:   # one process per size
+        which = "--components" if args.components else "--support" if args.support else "--paths" if args.paths else "--locate" if args.locate else "--text"
         res = []
         for n in args.reads:
             cmd = [sys.executable, os.path.abspath(__file__), "--child", which, "--k", str(args.k), "--reads", str(n)]
@@ -567,7 +697,7 @@ def main():
             except subprocess.TimeoutExpired:
                 res.append({"reads": n, "error": f"no result within {args.timeout} s"})
                 break
-        print(json.dumps({"probe": "unitig-link-support" if args.support else "unitig-paths" if args.paths else "unitig-locate" if args.locate else "unitig-text", "result": res}, indent=1))
+        print(json.dumps({"probe": "unitig-components" if args.components else "unitig-link-support" if args.support else "unitig-paths" if args.paths else "unitig-locate" if args.locate else "unitig-text", "result": res}, indent=1))
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--k", str(args.k)] + (["--clip"] if args.clip else []) + (["--pop"] if args.pop else []) + ["--reads"] + [str(n) for n in args.reads]
     try:
